@@ -13,6 +13,11 @@ the timed region.  Weak scaling: every rank owns 256 envs, so the node runs 256Â
 
 Rank 0 prints ONE JSON line; ``value`` = whole-node env-steps/s (max time over ranks).
 Baseline = 43 env-steps/s: the reference itself on the 32-worker config (CPU, measured).
+
+A plain run sets up, warms up, times ``--steps`` iterations and prints the line.  ``--full`` adds what takes runs of
+its own after the timed loop: the per-phase breakdown (``--steps`` more instrumented iterations) and the eval block
+(the reference benchmark sweep for a random-init policy, the trained checkpoints and the fixed heuristic).
+``--dump-outputs DIR`` writes what the last timed iteration left with its caller as ``DIR/<name>.npy``.
 """
 import argparse
 import json
@@ -41,10 +46,16 @@ def parse():
     p.add_argument("--num_mini_batch", type=int, default=4)
     p.add_argument("--kernels", default="auto")
     p.add_argument("--dtype", default="bf16")
-    p.add_argument("--phases", action="store_true", help="also print the phase summary to stderr")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed loop also run the phase breakdown and the eval block (each can still be "
+                        "switched off with --no_phase_timers / --no_eval); a plain run measures the headline only")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed (its training statistics, the updated parameters "
+                        "and the rollout it stored) as DIR/<name>.npy, at most 64 MB in all")
+    p.add_argument("--phases", action="store_true", help="also print the phase summary to stderr (with --full)")
     p.add_argument("--no_phase_timers", action="store_true",
-                   help="skip the phase breakdown (extra instrumented steps after the timed loop; the timed loop "
-                        "itself never records phase events)")
+                   help="with --full: skip the phase breakdown (extra instrumented steps after the timed loop; the "
+                        "timed loop itself never records phase events)")
     p.add_argument("--allreduce", default="rccl", choices=["rccl", "oneshot", "auto", "ordered"],
                    help="data-parallel gradient all-reduce: RCCL (default), the one-shot peer-memory kernel, auto "
                         "(one-shot only if it matches RCCL and is faster at start-up), or ordered (all-gather + "
@@ -55,10 +66,14 @@ def parse():
                    help="dcml: the headline 32-worker DCML config; smac: MAT on the SMAC-shaped 27m_vs_30m stress env")
     p.add_argument("--rollout_groups", type=int, default=1,
                    help="env groups of the pipelined rollout (each on its own stream; identical rollout)")
-    p.add_argument("--no_eval", action="store_true", help="skip the post-timing eval sweep (ct / payment / latency)")
+    p.add_argument("--no_eval", action="store_true",
+                   help="with --full: skip the post-timing eval sweep (ct / payment / latency)")
     p.add_argument("--model_dir", default=None,
                    help="trained checkpoint for the eval block (default: the committed 32-worker run, if it matches)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.phases and not (a.full and not a.no_phase_timers):
+        p.error("--phases prints the phase breakdown, which runs only with --full (and without --no_phase_timers)")
+    return a
 
 
 def launch_ranks(n):
@@ -95,8 +110,21 @@ def launch_ranks(n):
     return rc if rc >= 0 else 128 - rc
 
 
+def measure_the_built_library():
+    """Where this user cannot write the library's directory, the benchmark cannot rebuild the library anyway: hide
+    the compiler from the loader (``csrc/build.py`` reads ``HIPCC``), so that a stale library is reported as stale
+    instead of as a failed write, and nothing is compiled inside a run whose time is being measured.  This file is
+    also the yardstick for A/B runs against other revisions of the package (``scripts/build_ab.sh``); revisions whose
+    loader opens its rebuild lock before it checks the library could not load in such a tree at all without this.
+    Only set in that case, for this process and the rank processes it starts."""
+    lib_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mat_dcml_amd", "_lib")
+    if os.path.exists(os.path.join(lib_dir, "libmatdcml.so")) and not os.access(lib_dir, os.W_OK):
+        os.environ["HIPCC"] = os.path.join(lib_dir, "no-compiler-for-a-read-only-tree")
+
+
 def main():
     a = parse()
+    measure_the_built_library()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus))
     if a.config == "smac":
@@ -141,8 +169,9 @@ def main():
     sync()
     comm.enable_timing(True)   # hipEvents around the critical-path collectives (grad average, epoch statistics)
     t0 = time.perf_counter()
+    infos = None
     for _ in range(a.steps):
-        runner.train_iteration()
+        infos = runner.train_iteration()
     sync()
     t_rank = time.perf_counter() - t0      # this rank's own time, before waiting for the others
     comm.barrier()
@@ -160,11 +189,13 @@ def main():
                                  for k in ("grad_allreduce", "stats_allreduce")},
             "collectives_per_step": {k: max(r[1].get(k + "_calls", 0) for r in per_rank) // max(a.steps, 1)
                                      for k in ("grad_allreduce", "stats_allreduce")}}
-    phases = None if a.no_phase_timers else phase_breakdown(a, runner, comm, sync)
+    if a.dump_outputs and comm.is_main:   # before anything below runs the trainer again
+        dump_outputs(a.dump_outputs, runner, infos)
+    phases = phase_breakdown(a, runner, comm, sync) if a.full and not a.no_phase_timers else None
     env_steps = a.steps * a.episode_length * a.envs * n
     value = env_steps / dt
     eval_info = None
-    if not a.no_eval and comm.is_main and dev.type == "cuda":
+    if a.full and not a.no_eval and comm.is_main and dev.type == "cuda":
         eval_info = eval_block(a, args, runner, dev)
     if comm.is_main:
         if a.phases and phases:
@@ -229,6 +260,38 @@ def phase_breakdown(a, runner, comm, sync):
                                   "(every occurrence timed); train_fwd / train_bwd lie inside update"},
             "train_kernels_ms_per_minibatch": {k[6:]: round(tot[k] / n_mb, 4) for k in ("train_fwd", "train_bwd")
                                                if k in tot}}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_ROLLOUT = ("actions", "action_log_probs", "value_preds", "rewards", "returns", "advantages")
+
+
+def dump_outputs(out_dir, runner, infos):
+    """``--dump-outputs DIR``: what a caller of the timed path holds after the last timed ``train_iteration()``, one
+    float32 / float64 ``DIR/<name>.npy`` each: the training statistics it returned (``info_<key>``), the parameters
+    its update left (``params``, flat, in ``parameters()`` order) and the rollout it stored (``rollout_<field>``).
+    The env, the sampling noise and the initial weights are all seeded by the arguments, so two builds run with the
+    same arguments see identical inputs.  An array above its share of the 64 MB budget is written as a fixed seeded
+    sample of its elements (same indices for the same shape)."""
+    import numpy as np
+    arrays = {f"info_{k}": torch.as_tensor(v).detach().double().reshape(-1) for k, v in (infos or {}).items()}
+    arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in runner.policy.transformer.parameters()])
+    for name in DUMP_ROLLOUT:
+        arrays[f"rollout_{name}"] = getattr(runner.buffer, name).detach().float()
+    cap = DUMP_BUDGET_BYTES // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), sample_within(t.cpu().numpy(), cap))
+
+
+def sample_within(x, cap_bytes):
+    """``x`` itself when it fits in ``cap_bytes``; otherwise ``cap_bytes`` worth of its elements at distinct, sorted
+    flat indices drawn with a fixed seed (the same indices for the same size and cap)."""
+    import numpy as np
+    if x.nbytes <= cap_bytes:
+        return x
+    idx = np.sort(np.random.default_rng(0).choice(x.size, cap_bytes // x.itemsize, replace=False))
+    return x.reshape(-1)[idx]
 
 
 def _grad_path(tr, n):
@@ -338,14 +401,17 @@ def bench_smac(a):
         torch.cuda.synchronize(dev)
     comm.barrier()
     t0 = time.perf_counter()
+    infos = None
     for _ in range(a.steps):
-        runner.train_iteration()
+        infos = runner.train_iteration()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     comm.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     comm.all_reduce_max_(t)
     dt, n = float(t), comm.world_size
+    if a.dump_outputs and comm.is_main:
+        dump_outputs(a.dump_outputs, runner, infos)
     value = a.steps * T * envs * n / dt
     if comm.is_main:
         print(json.dumps({"metric": "env-steps/sec (whole node) MAT on SMAC 27m_vs_30m (synthetic SMAC-shaped env)",

@@ -110,7 +110,11 @@ def lib():
         b = _build_mod()
         # only the default library is rebuilt: a named variant (A/B timing builds, MAT_DCML_LIBNAME) was built with
         # flags the environment of this process need not carry, so "stale" there means "leave it alone"
-        if os.path.exists(b.HIPCC) and LIB_PATH == b.OUT and os.path.basename(LIB_PATH) == "libmatdcml.so":
+        rebuildable = os.path.exists(b.HIPCC) and LIB_PATH == b.OUT and os.path.basename(LIB_PATH) == "libmatdcml.so"
+        # a library whose sidecar matches the tree takes no lock: a user who cannot write the tree (built by another
+        # user, read-only checkout) still loads it; the sidecar is written after the library is in place
+        why = _sidecar_stale(b) if rebuildable else None
+        if why is not None:
             with _BuildLock(os.path.dirname(LIB_PATH)):
                 why = _sidecar_stale(b)   # re-checked under the lock: another rank may have just rebuilt it
                 if why is not None:

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Round-end rehearsal in one GPU call: every GPU test, smoke(), the driver's default bench (with the eval block),
-# a 2-rank launch rehearsal, and rocprofv3 kernel stats of the headline bench.
+# Round-end rehearsal in one GPU call: every GPU test, smoke(), the driver's default bench (the plain run: headline
+# only; the eval block and the phase breakdown are bench.py --full, which this script does not run), and rocprofv3
+# kernel stats of the headline bench.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out

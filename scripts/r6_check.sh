@@ -16,6 +16,7 @@ if [ -n "$TESTS" ]; then
   [ $rc -ne 0 ] && { grep -E "^E " gpurun_out/r6_tests.log | head -30; exit 2; }
 fi
 if [ -n "$BENCH" ]; then
+  BENCH_ARGS="--full $BENCH_ARGS"   # the phase figures printed below come from the --full run (the eval stays off)
   timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --no_eval $BENCH_ARGS > gpurun_out/r6_bench.log 2>&1 || { tail -20 gpurun_out/r6_bench.log; exit 3; }
   tail -1 gpurun_out/r6_bench.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('BENCH', d['value'], d['ms_per_step'], d.get('phase_ms_per_step'), d.get('train_kernels_ms_per_minibatch'))"
 fi

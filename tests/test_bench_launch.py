@@ -25,8 +25,8 @@ def _env(**kw):
 
 
 def test_bench_self_launches_two_ranks():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", *SMALL], cwd=ROOT, env=_env(), capture_output=True,
-                       text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", *SMALL], cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=600)   # --full: the phase breakdown is asserted below
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout          # rank 0 prints ONE JSON line
@@ -55,6 +55,71 @@ def test_bench_self_launches_two_ranks():
     assert top <= 1.02 * run["ms_per_step"]
     tk = out["train_kernels_ms_per_minibatch"]
     assert set(tk) == {"fwd", "bwd"} and abs(tk["fwd"] - ph["train_fwd"]) < 1e-2   # 1 epoch x 1 minibatch
+
+
+def test_plain_run_measures_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no ``--full``) reports the headline with neither the phase breakdown nor the eval block, times
+    exactly ``--steps`` steps, and ``--dump-outputs`` writes the last timed step's outputs as float32 / float64
+    ``.npy`` files: the same files with the same contents from two runs with the same arguments (CPU path: the
+    whole iteration is bit-reproducible)."""
+    import numpy as np
+    plain = ["--steps", "2", "--warmup", "1", "--envs", "4", "--episode_length", "2", "--n_workers", "4",
+             "--ppo_epoch", "1", "--num_mini_batch", "1"]
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *plain, "--dump-outputs", str(tmp_path / d)],
+                           cwd=ROOT, env=_env(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES=""), capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 2 * 4 / out["ms_per_step"] * 1e3) <= 0.01 * out["value"]   # env-steps / timed second
+    assert out["eval"] is None and "phase_ms_per_step" not in out and "phase_run" not in out
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert "params.npy" in names and "rollout_actions.npy" in names and "info_value_loss.npy" in names
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.size > 0 and np.isfinite(x).all(), n
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "rollout_actions.npy").shape[:3] == (2, 4, 5)   # (T, envs, agents)
+
+
+def test_dump_sample_is_fixed_distinct_and_within_its_cap():
+    """An output above its share of the dump budget is written as a sample: exactly the cap's worth of elements, at
+    distinct sorted positions, the same ones on every call; an output that fits is written whole."""
+    import numpy as np
+    import bench
+    x = np.arange(10007, dtype=np.float32)              # its own index as value: the sample shows the positions
+    s = bench.sample_within(x.reshape(10007, 1), 4000)
+    assert s.dtype == np.float32 and s.nbytes == 4000 and s.ndim == 1
+    assert np.all(np.diff(s) > 0)                       # sorted, no position twice
+    assert np.array_equal(s, bench.sample_within(x, 4000))
+    assert s.min() < 1000 and s.max() > 9000            # spread over the array, not a prefix
+    assert bench.sample_within(x, x.nbytes) is x
+
+
+def test_bench_hides_the_compiler_only_where_it_cannot_write_the_library(monkeypatch):
+    """bench.py hides the compiler from the loader only where the library exists and its directory cannot be written
+    (a stale library is then refused as stale: ``test_build_guard.test_stale_library_refused_without_hipcc``)."""
+    import bench
+    monkeypatch.setenv("HIPCC", "/some/hipcc")
+    monkeypatch.setattr(os.path, "exists", lambda p: True)
+    monkeypatch.setattr(os, "access", lambda p, mode: True)
+    bench.measure_the_built_library()
+    assert os.environ["HIPCC"] == "/some/hipcc"           # a writable tree keeps the compiler (and the rebuild)
+    monkeypatch.setattr(os, "access", lambda p, mode: False)
+    bench.measure_the_built_library()
+    hidden = os.environ["HIPCC"]
+    monkeypatch.undo()                                    # the real os.path.exists, and HIPCC as it was
+    assert hidden != "/some/hipcc" and not os.path.exists(hidden)
 
 
 def test_bench_rejects_world_size_mismatch():

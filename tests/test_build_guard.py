@@ -122,6 +122,25 @@ def test_missing_lib_dir_reaches_the_build(tmp_path):
     assert "rebuilding" in r.stdout and "BUILDFAIL" in r.stdout, r.stdout + r.stderr
 
 
+def test_fresh_library_loads_without_the_build_lock(tmp_path):
+    """A library whose identity matches the tree is loaded without opening ``_lib/.build.lock``: a user who cannot
+    write the tree (it was built by someone else) must still run the native code.  The lock path is a directory
+    here, so opening it fails for every user."""
+    pkg = tmp_path / "mat_dcml_amd"
+    shutil.copytree(os.path.join(ROOT, "mat_dcml_amd"), pkg,
+                    ignore=shutil.ignore_patterns("__pycache__", "obj", "libmatdcml_*.so", ".build.lock"))
+    (pkg / "_lib" / ".build.lock").mkdir()
+    code = ("from mat_dcml_amd.ops import kernels\n"
+            "kernels.lib()\nprint('LOADED', kernels.BUILD_ID, kernels.LIB_PATH)\n")
+    env = dict(os.environ, PYTHONPATH=str(tmp_path))
+    env.pop("MAT_DCML_LIBNAME", None)
+    env.pop("HIPCC", None)
+    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert "LOADED" in r.stdout and str(pkg) in r.stdout, r.stdout + r.stderr
+    assert "rebuilding" not in r.stdout
+
+
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_kernel_arg_structs_match_ctypes(tmp_path):
     """The ctypes mirrors of the kernel argument structs (EncP / DecP / PPOArgs / AdamArgs / UpdArgs) must have the C

@@ -9,13 +9,16 @@ policy has not moved — is 1 only up to that rounding.  This test rolls out wit
 the SAME observations / actions with the training forward, and bounds mean / max |Δ log-prob| and |mean ratio - 1|.
 """
 import math
+import os
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-CKPT32 = "profiles/r5_train32/transformer_500_beta3.pt"
+# anchored at the repository root: found from any working directory, so the trained case never skips by accident
+CKPT32 = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                      "profiles/r5_train32/transformer_500_beta3.pt")
 
 
 def _dcml_runner(dev, n_workers, envs, T):
