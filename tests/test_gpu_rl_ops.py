@@ -132,7 +132,9 @@ def test_masked_sums_and_gather_match_torch(gpu):
     act = torch.randn(T * E, A, 1, device=gpu, generator=g)
     adv_f = adv.reshape(T * E, A, 1)
     idx = torch.randperm(T * E, device=gpu, generator=g)[:800]
-    wide = torch.randn(T * E, A, 12, device=gpu, generator=g)   # row width % 4 == 0: the float4 path
+    # row width 33 x 12 = 396 < 1024: still the narrow element loop (the chunked float4 path of rows >= 1024 floats
+    # is covered by tests/test_gpu_rl_edges.py)
+    wide = torch.randn(T * E, A, 12, device=gpu, generator=g)
     out = kernels.gather_rows({"obs": obs, "actions": act, "adv": adv_f, "wide": wide}, idx, sums, ("adv",))
     assert torch.equal(out["obs"], obs[idx]) and torch.equal(out["actions"], act[idx])
     assert torch.equal(out["wide"], wide[idx])
