@@ -143,8 +143,30 @@ class MATTrainer:
             mat_train.attach_grad_workspace(m, flat.buf, copies=copies, mode=mode)
         # kernels that add into .grad directly, outside the workspace (the wide-observation embedding backward): the
         # flat buffer is then zeroed per minibatch and the reduction adds to it; otherwise the reduction overwrites
-        self._direct_grads = m.encoder.obs_dim > mat_train.MAX_FUSED_OBS or mode != "private" or copies <= 0
-        self.deterministic = mode == "private" and copies > 0 and not self._direct_grads
+        wide = m.encoder.obs_dim > mat_train.MAX_FUSED_OBS
+        self._direct_grads = wide or mode != "private" or copies <= 0
+        # what keeps the update from being bit-reproducible (None: it is).  The wide-observation embedding backward
+        # adds each .grad element once from fixed-order sums unless MAT_DCML_OBS_EMBED_GRAD=atomic
+        # (mat_train.ObsEmbed.grad_mode); with wide observations the claim covers the Discrete / Semi_Discrete
+        # decoders only: the Continuous decoder's action-embedding backward sums fp32 values into LDS with atomicAdd
+        # from its 8 waves (csrc/mat_dec_ct.hip)
+        self.obs_embed_grad = None
+        if wide:
+            enc = mat_train._state(m, self.device)[0]
+            if getattr(enc, "emb", None) is None:
+                enc.emb = mat_train.ObsEmbed(m)
+            self.obs_embed_grad = enc.emb.grad_mode
+        self.nondeterministic_writer = None
+        if mode != "private" or copies <= 0:
+            self.nondeterministic_writer = f"gradient workspace (mode {mode}, {copies} copies): fp32 global atomics"
+        elif wide:
+            if self.obs_embed_grad != "partials":
+                self.nondeterministic_writer = ("wide-observation embedding backward (csrc/obs_embed.hip, grad mode "
+                                                f"{self.obs_embed_grad}): fp32 global atomics")
+            elif m.action_type not in ("Discrete", "Semi_Discrete"):
+                self.nondeterministic_writer = (f"{m.action_type} decoder action-embedding backward with wide "
+                                                "observations (csrc/mat_dec_ct.hip): fp32 LDS atomics from 8 waves")
+        self.deterministic = self.nondeterministic_writer is None
         self._upd_fused = (mode == "private" and copies > 0 and self.comm.world_size == 1
                            and os.environ.get("MAT_DCML_FUSED_UPDATE", "1") != "0")
         # opt-in (MAT_DCML_GATHER_AHEAD=1): the next minibatch's gather on a side stream, overlapped with this
@@ -157,11 +179,13 @@ class MATTrainer:
         self.fused_gather = self.device.type == "cuda" and os.environ.get("MAT_DCML_FUSED_GATHER", "1") != "0"
         # the reference's cuda_deterministic (store_false: ON unless --cuda_deterministic is passed,
         # DCML_MAT_Train.py:108-110): the fused trainer's PPO update is bit-reproducible with the private gradient
-        # workspace (tests/test_gpu_determinism.py); wide observations keep fp32 atomics in their embedding backward
+        # workspace (tests/test_gpu_determinism.py), wide observations (SMAC, MPE) included: their embedding backward
+        # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py).  The warning names the writer
+        # that is order-dependent in the configurations left out
         if getattr(args, "cuda_deterministic", False) and not self.deterministic and self.device.type == "cuda":
             import warnings
-            warnings.warn("cuda_deterministic: this configuration's fused update is not bit-reproducible "
-                          f"(gradient mode {mode}, direct gradient writers {self._direct_grads})")
+            warnings.warn("cuda_deterministic: this configuration's fused update is not bit-reproducible: "
+                          + self.nondeterministic_writer)
         pol.optimizer = ppo_fused.FlatAdam(fp, flat.buf, lr=pol.optimizer.param_groups[0]["lr"], eps=args.opti_eps,
                                            weight_decay=args.weight_decay,
                                            max_grad_norm=args.max_grad_norm if self._use_max_grad_norm else None,

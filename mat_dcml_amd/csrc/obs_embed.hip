@@ -11,6 +11,9 @@
 // Backward (no gradient w.r.t. the data): with P_tf = dpre_tf r_t,
 //   M = Pᵀ x (64 x od, token reduction on MFMA),  u_f = Σ_t P_tf mu_t,  db_f = Σ_t dpre_tf,
 //   dW_fk = g_k (M_fk - u_f) + b_k db_f,   dg_k = Σ_f W_fk (M_fk - u_f),   db_obs_k = Σ_f W_fk db_f,   db_e = db.
+// The token reductions (M, u, db) run on many workgroups.  Default (OEArgs.mode 1): each stores its partial and one
+// kernel adds the partials in index order — bitwise repeatable; mode 0 adds them with fp32 atomics (kept for A/B runs).
+// The last kernel adds each gradient element into .grad exactly once, so it is order-free in either mode.
 #include "mat_train_common.h"
 
 namespace {
@@ -30,11 +33,15 @@ struct OEArgs {
   float* stat;                 // [N][2] mu, rstd
   // backward
   const float* dpre;           // [N][64]
-  float* M;                    // [64][od] workspace (zeroed by the host)
-  float* ud;                   // [2][64] u, db workspace (zeroed by the host)
+  float* M;                    // [64][od] workspace (mode 0: zeroed by the host; mode 1: written by the reduction)
+  float* ud;                   // [2][64] u, db workspace (likewise)
   float *d_we, *d_be, *d_g, *d_b;
   const bf16_t* xh;            // [N][od] bf16 observations (non-null: read instead of x — half the bytes, and x is
                                // exact in bf16 so the lo half of the hi / lo split vanishes)
+  // deterministic backward (mode 1): every workgroup stores its partial, one kernel sums them in index order
+  float* Mp;                   // [OEB_SPLIT][64][64 ceil(od / 64)] token-range partials of M (every slot written per call)
+  float* up;                   // [OEB_UBLK][128] per-workgroup partials of u, db
+  int mode;                    // 0: fp32 atomics into M / ud (zeroed by the host), 1: partials + fixed-order reduction
 };
 
 // W' = W_e diag(g) as bf16 A fragments + c1 (from the rounded values) / c0.  One block per output feature f.
@@ -242,6 +249,9 @@ __global__ __launch_bounds__(64 * OE_WAVES) void obs_embed_fwd_kernel(OEArgs a) 
 // global loads (float4 when od % 4 == 0) are issued before this tile's MFMAs; 64 token ranges per column block
 // (SMAC: 21 x 64 = 1,344 workgroups).  Round 2 (16 ranges, scalar loads, no prefetch) ran at ~0.4 TB/s: 628 us.
 constexpr int OEB_SPLIT = 64;   // token ranges per column block
+constexpr int OEB_UBLK = 256;   // workgroups of the u / db kernel
+constexpr int OEB_TS = 68;      // row stride (floats) of the partial tile's LDS transpose: 16-byte rows, and the 4 rows
+                                // a half-wave writes at once land on distinct banks
 struct OEBTile { float p[8], x[8]; };
 __device__ __forceinline__ void oeb_load(const OEArgs& a, int t, int t_hi, int col0, OEBTile& T) {
   const int lc = threadIdx.x & 7;
@@ -276,8 +286,15 @@ __device__ __forceinline__ void oeb_load(const OEArgs& a, int t, int t_hi, int c
     for (int j = 0; j < 8; ++j) { T.p[j] = 0.f; T.x[j] = 0.f; }
   }
 }
-__global__ __launch_bounds__(256) void obs_embed_bwd_m_kernel(OEArgs a) {
-  __shared__ __attribute__((aligned(16))) bf16_t Pt[32 * 64], Xh[32 * 64], Xl[32 * 64];
+// PART: the accumulator tile goes, through LDS (row-major, so the stores are 16 bytes along k), to this token range's
+// slab of Mp with plain stores — no atomics, no host memset; an empty range stores zeros.  The tile's LDS reuses the
+// staging buffers' (all their reads are behind the loop's closing barrier).
+template <bool PART>
+__device__ __forceinline__ void oeb_m_body(const OEArgs& a) {
+  __shared__ __attribute__((aligned(16))) float sm[PART ? 64 * OEB_TS : 3 * 32 * 64 / 2];
+  bf16_t* const Pt = (bf16_t*)sm;
+  bf16_t* const Xh = Pt + 32 * 64;
+  bf16_t* const Xl = Xh + 32 * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c16 = lane & 15, g = lane >> 4;
   const int col0 = blockIdx.x * 64;
   const int t_lo = (int)((long long)a.N * blockIdx.y / OEB_SPLIT), t_hi = (int)((long long)a.N * (blockIdx.y + 1) / OEB_SPLIT);
@@ -320,8 +337,26 @@ __global__ __launch_bounds__(256) void obs_embed_bwd_m_kernel(OEArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int f = 16 * wave + 4 * g + r, k = col0 + 16 * ct + c16;
-      if (k < a.od) atomicAdd(a.M + (size_t)f * a.od + k, acc.v[ct][r]);
+      if (PART) sm[f * OEB_TS + 16 * ct + c16] = acc.v[ct][r];
+      else if (k < a.od) atomicAdd(a.M + (size_t)f * a.od + k, acc.v[ct][r]);
     }
+  if (PART) {
+    __syncthreads();
+    const size_t odp = (size_t)gridDim.x * 64;
+    float* dst = a.Mp + (size_t)blockIdx.y * 64 * odp + col0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {   // 256 threads x 4 float4 = the 64 x 64 tile, 16 threads per row
+      const int e = threadIdx.x + 256 * i, f = e >> 4, c4 = (e & 15) << 2;
+      *(float4*)(dst + (size_t)f * odp + c4) = *(const float4*)(sm + f * OEB_TS + c4);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void obs_embed_bwd_m_kernel(OEArgs a) { oeb_m_body<false>(a); }
+// At least 6 workgroups per CU, so that SMAC's 1,344 workgroups are resident at once on 256 CUs.  Without the bound
+// the epilogue's 2 extra VGPRs (66 + 16 AGPRs) left 5 per CU and a second round of 64 workgroups: 132.6 us at the
+// 86,400-token minibatch; with it (64 VGPRs, no AGPRs) 92.1 us, the atomic kernel 108.7 (profiles/obs_embed_det/)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void obs_embed_bwd_m_part_kernel(OEArgs a) {
+  oeb_m_body<true>(a);
 }
 
 // backward step 1b: u_f = Σ_t dpre_tf r_t mu_t and db_f = Σ_t dpre_tf (thread = (token lane, feature))
@@ -341,9 +376,38 @@ __global__ __launch_bounds__(256) void obs_embed_bwd_u_kernel(OEArgs a) {
   sd[tl][f] = d;
   __syncthreads();
   if (tl == 0) {
-    atomicAdd(a.ud + f, su[0][f] + su[1][f] + su[2][f] + su[3][f]);
-    atomicAdd(a.ud + 64 + f, sd[0][f] + sd[1][f] + sd[2][f] + sd[3][f]);
+    const float us = su[0][f] + su[1][f] + su[2][f] + su[3][f], ds = sd[0][f] + sd[1][f] + sd[2][f] + sd[3][f];
+    if (a.mode) {   // this workgroup's partial (zeros when it had no token)
+      a.up[(size_t)blockIdx.x * 128 + f] = us;
+      a.up[(size_t)blockIdx.x * 128 + 64 + f] = ds;
+    } else {
+      atomicAdd(a.ud + f, us);
+      atomicAdd(a.ud + 64 + f, ds);
+    }
   }
+}
+
+// backward step 1c (mode 1): M = Σ Mp slabs in ascending token-range index, ud = Σ up in ascending workgroup index.
+// One thread per output element (blockIdx.y = feature row, threads along k); blockIdx.y == 64: u / db.  Grid and order
+// depend on od alone, so the sums are bitwise repeatable.
+__global__ __launch_bounds__(256) void obs_embed_bwd_red_kernel(OEArgs a) {
+  if (blockIdx.y == 64) {
+    if (blockIdx.x == 0 && threadIdx.x < 128) {
+      float s = 0.f;
+#pragma unroll 16
+      for (int w = 0; w < OEB_UBLK; ++w) s += a.up[(size_t)w * 128 + threadIdx.x];
+      a.ud[threadIdx.x] = s;
+    }
+    return;
+  }
+  const int k = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+  if (k >= a.od) return;
+  const size_t odp = (size_t)((a.od + 63) / 64) * 64;
+  const float* src = a.Mp + (size_t)f * odp + k;
+  float s = 0.f;
+#pragma unroll 16   // 16 slabs' loads in flight, added in slab order
+  for (int y = 0; y < OEB_SPLIT; ++y) s += src[(size_t)y * 64 * odp];
+  a.M[(size_t)f * a.od + k] = s;
 }
 
 // backward step 2: parameter gradients from M, u, db (one thread per obs dim k; d_be by the first 64 threads)
@@ -390,12 +454,24 @@ MDL_API int mdl_obs_embed_fwd(const OEArgs* a, hipStream_t st) {
 
 MDL_API int mdl_obs_embed_bwd(const OEArgs* a, hipStream_t st) {
   if (a->N <= 0) return 0;
-  hipMemsetAsync(a->M, 0, sizeof(float) * 64 * (size_t)a->od, st);
-  hipMemsetAsync(a->ud, 0, sizeof(float) * 128, st);
-  hipLaunchKernelGGL(obs_embed_bwd_m_kernel, dim3((a->od + 63) / 64, OEB_SPLIT), dim3(256), 0, st, *a);
-  MDL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(obs_embed_bwd_u_kernel, dim3(256), dim3(256), 0, st, *a);
-  MDL_CHECK_LAUNCH();
+  if (a->mode != 0 && a->mode != 1) return -1;
+  if (a->mode == 1 && (!a->Mp || !a->up)) return -1;
+  const dim3 mgrid((a->od + 63) / 64, OEB_SPLIT);
+  if (a->mode == 1) {
+    hipLaunchKernelGGL(obs_embed_bwd_m_part_kernel, mgrid, dim3(256), 0, st, *a);
+    MDL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(obs_embed_bwd_u_kernel, dim3(OEB_UBLK), dim3(256), 0, st, *a);
+    MDL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(obs_embed_bwd_red_kernel, dim3((a->od + 255) / 256, 65), dim3(256), 0, st, *a);
+    MDL_CHECK_LAUNCH();
+  } else {
+    hipMemsetAsync(a->M, 0, sizeof(float) * 64 * (size_t)a->od, st);
+    hipMemsetAsync(a->ud, 0, sizeof(float) * 128, st);
+    hipLaunchKernelGGL(obs_embed_bwd_m_kernel, mgrid, dim3(256), 0, st, *a);
+    MDL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(obs_embed_bwd_u_kernel, dim3(OEB_UBLK), dim3(256), 0, st, *a);
+    MDL_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(obs_embed_bwd_fin_kernel, dim3((a->od + 255) / 256), dim3(256), 0, st, *a);
   MDL_CHECK_LAUNCH();
   return 0;

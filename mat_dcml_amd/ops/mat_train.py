@@ -84,7 +84,7 @@ sig("mdl_ct_bwd_grid", ctypes.c_int, ctypes.c_int)
 class OEArgs(ctypes.Structure):   # csrc/obs_embed.hip
     _fields_ = [(n, ctypes.c_int) for n in ("N", "od", "KS")] + \
                [(n, VP) for n in ("x", "we", "be", "g", "b", "wpack", "c01", "pre", "stat", "dpre", "M", "ud", "d_we",
-                                  "d_be", "d_g", "d_b", "xh")]
+                                  "d_be", "d_g", "d_b", "xh", "Mp", "up")] + [("mode", ctypes.c_int)]
 
 
 sig("mdl_obs_embed_pack", ctypes.POINTER(OEArgs), VP)
@@ -95,11 +95,17 @@ MAX_FUSED_OBS = 16      # obs_dim embedded inside the fused encoder; wider obser
 # Rollout and learner both round them, so the PPO ratio is unaffected (tests/test_gpu_logprob_consistency.py smac).
 # SMAC bench 75.8k / 76.8k -> 77.8k / 77.8k env-steps/s (profiles/r6_ab/).  MAT_DCML_WIDE_OBS_BF16=0: fp32 inputs.
 WIDE_OBS_BF16 = os.environ.get("MAT_DCML_WIDE_OBS_BF16", "1") == "1"
+OEB_SPLIT, OEB_UBLK = 64, 256   # csrc/obs_embed.hip: token ranges per column block, workgroups of the u / db kernel
 
 
 class ObsEmbed:
     """LN(obs_dim) -> Linear(obs_dim, 64) pre-activation on MFMA for wide observations (SMAC), with the LayerNorm
-    folded into the GEMM (csrc/obs_embed.hip); its W' pack is refreshed once per optimizer step."""
+    folded into the GEMM (csrc/obs_embed.hip); its W' pack is refreshed once per optimizer step.
+
+    ``grad_mode``: how the backward's token reductions are summed.  ``"partials"`` (default): every workgroup stores
+    its partial into ``Mp`` / ``up`` and one kernel adds them in index order — bitwise repeatable.  ``"atomic"``
+    (``MAT_DCML_OBS_EMBED_GRAD=atomic``, read when the object is built): fp32 atomics, for A/B runs.  The partial
+    workspaces (SMAC: 22 MB) are allocated by the first backward, so rollout-only and eval processes never hold them."""
 
     def __init__(self, model):
         enc = model.encoder
@@ -112,6 +118,10 @@ class ObsEmbed:
         self.c01 = torch.empty(128, device=dev)
         self.M = torch.empty(64 * self.od, device=dev)
         self.ud = torch.empty(128, device=dev)
+        self.grad_mode = os.environ.get("MAT_DCML_OBS_EMBED_GRAD", "partials")
+        if self.grad_mode not in ("partials", "atomic"):
+            raise ValueError(f"MAT_DCML_OBS_EMBED_GRAD={self.grad_mode}: expected 'partials' or 'atomic'")
+        self.Mp = self.up = None
         self.version = None
 
     def _args(self, N=0, x=None, pre=None, stat=None, dpre=None):
@@ -123,7 +133,8 @@ class ObsEmbed:
                       g=self.ln.weight.data_ptr(), b=self.ln.bias.data_ptr(), wpack=self.wpack.data_ptr(),
                       c01=self.c01.data_ptr(), pre=_ptr(pre), stat=_ptr(stat), dpre=_ptr(dpre), M=self.M.data_ptr(),
                       ud=self.ud.data_ptr(), d_we=_gptr(self.lin.weight), d_be=_gptr(self.lin.bias),
-                      d_g=_gptr(self.ln.weight), d_b=_gptr(self.ln.bias))
+                      d_g=_gptr(self.ln.weight), d_b=_gptr(self.ln.bias), Mp=_ptr(self.Mp), up=_ptr(self.up),
+                      mode=int(self.grad_mode == "partials"))
 
     def refresh(self):
         ver = getattr(self.model, "_mdl_version", 0)
@@ -142,6 +153,10 @@ class ObsEmbed:
         return pre, stat
 
     def backward(self, obs2d, stat, dpre):
+        if self.grad_mode == "partials" and self.Mp is None:
+            dev = self.M.device
+            self.Mp = torch.empty(OEB_SPLIT * 64 * 64 * ((self.od + 63) // 64), device=dev)
+            self.up = torch.empty(OEB_UBLK * 128, device=dev)
         a = self._args(obs2d.shape[0], obs2d, None, stat, dpre)
         check(lib().mdl_obs_embed_bwd(ctypes.byref(a), kernels._stream()), "obs_embed_bwd")
 sig("mdl_pack_weights", VP, ctypes.c_int, VP)

@@ -65,6 +65,8 @@ def kernel_report(runner) -> dict:
         tr = getattr(runner, "trainer", None)
         if tr is not None and getattr(tr, "fused", False):
             out["train"] = "hip:mat_enc_fwd/bwd+mat_dec_fwd/bwd+ppo_loss+adam"
+            if getattr(tr, "obs_embed_grad", None):   # wide observations: how the embedding backward sums
+                out["train"] += f"+obs_embed_fwd/bwd[grad={tr.obs_embed_grad}]"
         elif not reason and getattr(pol, "_enc_fused", lambda: False)() and mat_train.decoder_unsupported_reasons(m):
             # ops/mat_fused.evaluate_actions: fused encoder kernels under autograd, eager decoder
             out["train"] = "hybrid: hip:mat_enc_fwd/bwd + torch decoder (" + \
@@ -92,5 +94,9 @@ def log_kernel_report(runner, stream=None):
     import sys
     rep = kernel_report(runner)
     if getattr(runner, "comm", None) is None or runner.comm.is_main:
-        print("[kernels] " + ", ".join(f"{k}={v}" for k, v in rep.items()), file=stream or sys.stdout, flush=True)
+        line = "[kernels] " + ", ".join(f"{k}={v}" for k, v in rep.items())
+        tr = getattr(runner, "trainer", None)
+        if getattr(tr, "fused", False):   # the fused update's bit-reproducibility (MATTrainer.deterministic)
+            line += ", deterministic=" + ("yes" if tr.deterministic else f"no ({tr.nondeterministic_writer})")
+        print(line, file=stream or sys.stdout, flush=True)
     return rep
