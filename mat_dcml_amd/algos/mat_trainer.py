@@ -147,9 +147,10 @@ class MATTrainer:
         self._direct_grads = wide or mode != "private" or copies <= 0
         # what keeps the update from being bit-reproducible (None: it is).  The wide-observation embedding backward
         # adds each .grad element once from fixed-order sums unless MAT_DCML_OBS_EMBED_GRAD=atomic
-        # (mat_train.ObsEmbed.grad_mode); with wide observations the claim covers the Discrete / Semi_Discrete
-        # decoders only: the Continuous decoder's action-embedding backward sums fp32 values into LDS with atomicAdd
-        # from its 8 waves (csrc/mat_dec_ct.hip)
+        # (mat_train.ObsEmbed.grad_mode).  The claim covers every action type the fused trainer accepts — Discrete,
+        # Semi_Discrete and Continuous (its action-embedding backward is an MFMA weight-gradient product flushed like
+        # every other weight gradient, csrc/mat_dec_ct.hip); Available_Continuous and dec_actor train through the
+        # hybrid path (self.fused is False, eager decoder) and make no such claim
         self.obs_embed_grad = None
         if wide:
             enc = mat_train._state(m, self.device)[0]
@@ -159,13 +160,9 @@ class MATTrainer:
         self.nondeterministic_writer = None
         if mode != "private" or copies <= 0:
             self.nondeterministic_writer = f"gradient workspace (mode {mode}, {copies} copies): fp32 global atomics"
-        elif wide:
-            if self.obs_embed_grad != "partials":
-                self.nondeterministic_writer = ("wide-observation embedding backward (csrc/obs_embed.hip, grad mode "
-                                                f"{self.obs_embed_grad}): fp32 global atomics")
-            elif m.action_type not in ("Discrete", "Semi_Discrete"):
-                self.nondeterministic_writer = (f"{m.action_type} decoder action-embedding backward with wide "
-                                                "observations (csrc/mat_dec_ct.hip): fp32 LDS atomics from 8 waves")
+        elif wide and self.obs_embed_grad != "partials":
+            self.nondeterministic_writer = ("wide-observation embedding backward (csrc/obs_embed.hip, grad mode "
+                                            f"{self.obs_embed_grad}): fp32 global atomics")
         self.deterministic = self.nondeterministic_writer is None
         self._upd_fused = (mode == "private" and copies > 0 and self.comm.world_size == 1
                            and os.environ.get("MAT_DCML_FUSED_UPDATE", "1") != "0")
@@ -180,8 +177,10 @@ class MATTrainer:
         # the reference's cuda_deterministic (store_false: ON unless --cuda_deterministic is passed,
         # DCML_MAT_Train.py:108-110): the fused trainer's PPO update is bit-reproducible with the private gradient
         # workspace (tests/test_gpu_determinism.py), wide observations (SMAC, MPE) included: their embedding backward
-        # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py).  The warning names the writer
-        # that is order-dependent in the configurations left out
+        # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py), and the Continuous action type
+        # (MA-MuJoCo, tests/test_gpu_continuous_det.py).  The warning names the order-dependent writer of the opt-outs
+        # (MAT_DCML_GRAD_MODE=atomic, MAT_DCML_OBS_EMBED_GRAD=atomic); the hybrid path (Available_Continuous,
+        # dec_actor: eager decoder) is outside the claim and reports nothing here
         if getattr(args, "cuda_deterministic", False) and not self.deterministic and self.device.type == "cuda":
             import warnings
             warnings.warn("cuda_deterministic: this configuration's fused update is not bit-reproducible: "

@@ -482,7 +482,8 @@ __device__ __forceinline__ void head_fwd_ct(const DecP& p, const CT* xr, bool sa
   }
 }
 
-// LDS vector slots of the small weight gradients (wgrad_g_vacc): d W_a (A+1 slots), d W_h2 (A slots), d b_h2 (1), after
+// LDS vector slots of the small weight gradients (wgrad_g_vacc): d W_a (A+1 slots; continuous: A slots, then d b_a),
+// d W_h2 (A slots), d b_h2 (1), after
 // the 5 + 6 NB LayerNorm / log_std slots; -1 when they do not fit (A > 2 or NB = 3: per-chunk private / atomic flush)
 #ifndef MDL_SMALL_WG_VACC
 #define MDL_SMALL_WG_VACC 1
@@ -825,50 +826,74 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
       else wgrad_g(c.DA, c.XB, c.KP, c.g(p.d_wa), p.A + 1, 64, p.A + 1, nullptr, c.wave, lane, c.gm, c.DQ);
     }
   } else {
-    float* EMB = (float*)c.QB;   // [(A+1)][64] f32 accumulators (QB + KB: 2 NRP x 128 B >= 65 x 256 B)
-    for (int i = c.tid; i < (p.A + 1) * 64; i += NTHR) EMB[i] = 0.f;
-    __syncthreads();
+    // continuous actions: dW_a (64 x A) = Σ_rows d pre ⊗ a_prev and db_a = Σ_rows d pre — the same weight-gradient
+    // GEMM on MFMA (wgrad_g) with the previous agent's action vector as X (a zero row for a sequence's first token:
+    // it reaches db_a only).  Actions are arbitrary fp32 values, so X is a hi / lo bf16 pair like d pre (the lo
+    // tile in QB, free after the blocks): Yhi·Xhi + Ylo·Xhi + Yhi·Xlo in one pass, one flush.  No floating-point
+    // atomic sums in LDS (fp32 atomicAdd from the 8 waves made the sum's order, and its last bits, vary by run)
+    // opaque lane (as for the blocks): this phase's lane-derived addresses are otherwise computed at the kernel's start
+    // and held, or spilled, across all of it
+    Ctx ce = c;
+    asm volatile("" : "+v"(ce.lane), "+v"(ce.tid));
+    const int lane = ce.lane, g = lane >> 4;
     CT dlg, dlb;
     ct_zero(dlg);
     ct_zero(dlb);
     const CT gam = ld_vec(p.lnd_g, lane), bet = ld_vec(p.lnd_b, lane);
-    const int g = lane >> 4;
+    // rows [16 NT, KP) of QB: no row tile writes them and the attention passes leave their own values there
+    for (int i = ce.tid; i < (ce.KP - 16 * ce.NT) * 8; i += NTHR)
+      *(uint4*)(ce.QB + (size_t)16 * ce.NT * 64 + (size_t)i * 8) = make_uint4(0, 0, 0, 0);
+    // X first, in a pass of its own: the action loads and their split are not live across the LayerNorm backward
 #pragma unroll
     for (int k = 0; k < MAXRT; ++k) {
-      const int rt = c.wave + NW * k;
-      if (rt < c.NT) {
-        const bool ok = tok_ok(rt, c);
+      const int rt = ce.wave + NW * k;
+      if (rt < ce.NT) {
+        const bool ok = tok_ok(rt, ce);
+        const int row = rt * 16 + (lane & 15);
+        const bool has_prev = ok && row % ce.L != 0;
+        const float* prev = p.act + (has_prev ? src_tok(p.sidx, (size_t)(ce.tok0 + row), ce.L) - 1 : 0) * p.A;
+        CT ap;   // a_prev in the feature slots: element 16 mt + 4 g + r (< A)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int a = 16 * mt + 4 * g + r;
+            ap.v[mt][r] = (mt < MA && has_prev && a < p.A) ? prev[a] : 0.f;
+          }
+        CTr ah, al;
+        ct_split(ap, ah, al);
+        st_lds(ce.XB, rt, ah, ok, lane);   // X (hi) = previous-action rows
+        st_lds(ce.QB, rt, al, ok, lane);   // X (lo)
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < MAXRT; ++k) {
+      const int rt = ce.wave + NW * k;
+      if (rt < ce.NT) {
+        const bool ok = tok_ok(rt, ce);
         int tk;
-        CT e = dec_embed_pre_ct<CONT>(p, rt, tk, c), egp, xh, yy, de;
+        CT e = dec_embed_pre_ct<CONT>(p, rt, tk, ce), egp, xh, yy, de;
         gelu_ct_both(e, egp);
         const float rs = ln_fwd_ct(e, xh, yy, gam, bet);
         ln_bwd_ct(dx[k], xh, rs, gam, ok, de, dlg, dlb);
-        if (ok) {   // EMB[k][f] += d pre_f * a_prev_k (k < A), EMB[A][f] += d pre_f (bias)
-          const int row = rt * 16 + (lane & 15);
-          const bool first = row % c.L == 0;
-          const float* prev = p.act + (first ? 0 : src_tok(p.sidx, (size_t)(c.tok0 + row), c.L) - 1) * p.A;
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
+        for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float dp = de.v[mt][r] * egp.v[mt][r];
-              const int f = 16 * mt + 4 * g + r;
-              atomicAdd(EMB + p.A * 64 + f, dp);
-              if (!first)
-                for (int kk = 0; kk < p.A; ++kk) atomicAdd(EMB + kk * 64 + f, dp * prev[kk]);
-            }
-        }
+          for (int r = 0; r < 4; ++r) de.v[mt][r] = ok ? de.v[mt][r] * egp.v[mt][r] : 0.f;
+        CTr dh, dl;
+        ct_split(de, dh, dl);
+        st_lds(ce.DA, rt, dh, ok, lane);   // dY (hi)
+        st_lds(ce.DQ, rt, dl, ok, lane);   // dY (lo)
       }
     }
-    flush_vec(dlg, c.g(p.d_lnd_g), 2, c);
-    flush_vec(dlb, c.g(p.d_lnd_b), 3, c);
+    flush_vec(dlg, ce.g(p.d_lnd_g), 2, ce);
+    flush_vec(dlb, ce.g(p.d_lnd_b), 3, ce);
     __syncthreads();
-    for (int i = c.tid; i < (p.A + 1) * 64; i += NTHR) {   // W_a [64][A] and b_a
-      const int t = i / 64, col = i % 64;
-      float* d = t < p.A ? (p.d_wa ? c.g(p.d_wa) + col * p.A + t : nullptr) : (p.d_ba ? c.g(p.d_ba) + col : nullptr);
-      if (!d) continue;
-      if (c.gm.priv) priv_st1(d, EMB[i], (c.gm.first || !PRIV_LOADS) ? 0.f : priv_ld1(d), c.gm.first);   // owner thread
-      else atomicAdd(d, EMB[i]);
+    if (p.d_wa || p.d_ba) {
+      // W_a [64][A] (row stride A) and b_a: LDS slots vs0 .. vs0 + A - 1 and vs0 + A (the A + 1 slots the discrete
+      // table takes), or one read-modify-write of a private copy per chunk
+      if (vs0 >= 0) wgrad_g_vacc(ce.DA, ce.XB, ce.KP, ce.g(p.d_wa), p.A, 64, p.A, ce.g(p.d_ba), vs0, vs0 + p.A, ce, ce.DQ, ce.QB);
+      else wgrad_g(ce.DA, ce.XB, ce.KP, ce.g(p.d_wa), p.A, 64, p.A, ce.g(p.d_ba), ce.wave, lane, ce.gm, ce.DQ, ce.QB);
     }
   }
   CP_MARK(30);

@@ -527,8 +527,12 @@ __device__ __forceinline__ f32x4* frag_slot(float* dW, int wave, int lane, int j
 // Y2 (optional): a second dY tile added in the same pass (the lo half of a hi / lo split dY) — one flush instead of
 // two, so a private copy is read-modified-written once per chunk (two passes made the second pass's loads wait for
 // the first pass's stores to the same addresses: ~6 us per chunk in the decoder's embedding backward)
+// X2 (optional): a second X tile (the lo half of a hi / lo split X: arbitrary fp32 inputs such as continuous actions,
+// unlike one-hot rows, lose 8 mantissa bits in one bf16) — Y·X2 joins the same accumulators, so the pass computes
+// Y·X + Y2·X + Y·X2 (the Y2·X2 term, <= 2^-16 relative, is dropped); with Y2 the bias gradient sums Y + Y2
 __device__ __forceinline__ void wgrad_g(const bf16_t* Y, const bf16_t* X, int KP, float* dW, int ld, int nrows, int ncols,
-                                        float* db, int wave, int lane, GradMode gm, const bf16_t* Y2 = nullptr) {
+                                        float* db, int wave, int lane, GradMode gm, const bf16_t* Y2 = nullptr,
+                                        const bf16_t* X2 = nullptr) {
   static_assert(NW % 4 == 0, "row block per wave");
   constexpr int NCT = (16 + NW - 1) / NW;           // column tiles per wave (at most)
   const int rb = wave & 3;
@@ -567,9 +571,13 @@ __device__ __forceinline__ void wgrad_g(const bf16_t* Y, const bf16_t* X, int KP
         const bf16x8 b = ld_frag_T(X, k0, 16 * ct, lane);
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j], 0, 0, 0);
         if (Y2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b, acc[j], 0, 0, 0);
+        if (X2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ld_frag_T(X2, k0, 16 * ct, lane), acc[j], 0, 0, 0);
       }
     }
-    if (db) accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ones, accb, 0, 0, 0);
+    if (db) {
+      accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ones, accb, 0, 0, 0);
+      if (Y2) accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, ones, accb, 0, 0, 0);
+    }
   }
   if (dW && gm.priv) {
 #pragma unroll
@@ -614,7 +622,7 @@ __device__ __forceinline__ void wgrad_g(const bf16_t* Y, const bf16_t* X, int KP
 // gradient db (nrows floats) takes slot bslot.
 __device__ __forceinline__ void wgrad_g_vacc(const bf16_t* Y, const bf16_t* X, int KP, float* dW, int ld, int nrows,
                                              int ncols, float* db, int slot0, int bslot, const Ctx& c,
-                                             const bf16_t* Y2 = nullptr) {
+                                             const bf16_t* Y2 = nullptr, const bf16_t* X2 = nullptr) {
   constexpr int NCT = (16 + NW - 1) / NW;
   const int wave = c.wave, lane = c.lane, rb = wave & 3;
   if (wave >= 4) db = nullptr;
@@ -637,9 +645,13 @@ __device__ __forceinline__ void wgrad_g_vacc(const bf16_t* Y, const bf16_t* X, i
         const bf16x8 b = ld_frag_T(X, k0, 16 * ct, lane);
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j], 0, 0, 0);
         if (Y2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b, acc[j], 0, 0, 0);
+        if (X2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ld_frag_T(X2, k0, 16 * ct, lane), acc[j], 0, 0, 0);
       }
     }
-    if (db) accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ones, accb, 0, 0, 0);
+    if (db) {
+      accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ones, accb, 0, 0, 0);
+      if (Y2) accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, ones, accb, 0, 0, 0);
+    }
   }
   const int total = nrows * ld;
   if (dW) {
