@@ -148,9 +148,11 @@ class MATTrainer:
         # what keeps the update from being bit-reproducible (None: it is).  The wide-observation embedding backward
         # adds each .grad element once from fixed-order sums unless MAT_DCML_OBS_EMBED_GRAD=atomic
         # (mat_train.ObsEmbed.grad_mode).  The claim covers every action type the fused trainer accepts — Discrete,
-        # Semi_Discrete and Continuous (its action-embedding backward is an MFMA weight-gradient product flushed like
-        # every other weight gradient, csrc/mat_dec_ct.hip); Available_Continuous and dec_actor train through the
-        # hybrid path (self.fused is False, eager decoder) and make no such claim
+        # Semi_Discrete, Continuous and, with MAT_DCML_AVAIL_CONT_TRAIN=fused and 3 <= action_dim <= 16,
+        # Available_Continuous (their action-embedding backward is an MFMA weight-gradient product flushed like every
+        # other weight gradient, csrc/mat_dec_ct.hip).  Available_Continuous without the switch (the default) or with
+        # another action_dim, and dec_actor, train through the hybrid path (self.fused is False, eager decoder) and
+        # make no such claim
         self.obs_embed_grad = None
         if wide:
             enc = mat_train._state(m, self.device)[0]
@@ -177,10 +179,12 @@ class MATTrainer:
         # the reference's cuda_deterministic (store_false: ON unless --cuda_deterministic is passed,
         # DCML_MAT_Train.py:108-110): the fused trainer's PPO update is bit-reproducible with the private gradient
         # workspace (tests/test_gpu_determinism.py), wide observations (SMAC, MPE) included: their embedding backward
-        # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py), and the Continuous action type
-        # (MA-MuJoCo, tests/test_gpu_continuous_det.py).  The warning names the order-dependent writer of the opt-outs
-        # (MAT_DCML_GRAD_MODE=atomic, MAT_DCML_OBS_EMBED_GRAD=atomic); the hybrid path (Available_Continuous,
-        # dec_actor: eager decoder) is outside the claim and reports nothing here
+        # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py), the Continuous action type
+        # (MA-MuJoCo, tests/test_gpu_continuous_det.py) and Available_Continuous on the fused decoder kernels
+        # (MAT_DCML_AVAIL_CONT_TRAIN=fused, 3 <= action_dim <= 16, tests/test_gpu_avail_cont_train.py).  The warning
+        # names the order-dependent writer of the opt-outs (MAT_DCML_GRAD_MODE=atomic, MAT_DCML_OBS_EMBED_GRAD=atomic);
+        # the hybrid path (Available_Continuous by default, dec_actor: eager decoder) is outside the claim and reports
+        # nothing here
         if getattr(args, "cuda_deterministic", False) and not self.deterministic and self.device.type == "cuda":
             import warnings
             warnings.warn("cuda_deterministic: this configuration's fused update is not bit-reproducible: "

@@ -21,12 +21,32 @@ __device__ __forceinline__ int dec_token_ct(const DecP& p, int tok, int i) {
 
 // x0 pre-activation = W_a · onehot(token) — a column gather of W_a [64][A+1]; continuous action type:
 // W_a · a_prev + b_a with a_prev the previous agent's action vector (zero for row 0)
-template <bool CONT>
+// Available_Continuous: W_a [64][A+1] · (start flag, a_prev), no bias — column 0 for a sequence's first row, columns
+// 1 .. A times the previous agent's action vector (one-hot choice, then the continuous dimensions) for the others
+template <bool CONT, bool AV = false>
 __device__ __forceinline__ CT dec_embed_pre_ct(const DecP& p, int rt, int& tokid, const Ctx& c) {
   const int lane = c.lane, g = lane >> 4;
   const int row = rt * 16 + (lane & 15);
   const bool ok = row < c.NR;
   CT pre;
+  if (AV) {
+    tokid = -1;
+    const bool first = !ok || row % c.L == 0;
+    const float* prev = p.act + (first ? 0 : src_tok(p.sidx, (size_t)(c.tok0 + row), c.L) - 1) * p.A;
+    const int ld = p.A + 1;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pre.v[mt][r] = first ? p.wa[(16 * mt + 4 * g + r) * ld] : 0.f;
+    for (int k = 0; k < p.A; ++k) {
+      const float x = first ? 0.f : prev[k];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pre.v[mt][r] += p.wa[(16 * mt + 4 * g + r) * ld + 1 + k] * x;
+    }
+    return pre;
+  }
   if (CONT) {
     tokid = -1;
     const bool first = !ok || row % c.L == 0;
@@ -410,7 +430,25 @@ constexpr float HALF_LOG_2PI = 0.91893853320467274f;
 // itself (round 1 read a per-minibatch torch copy: three launches per minibatch)
 __device__ __forceinline__ float head_sd(const DecP& p, int a) { return 0.5f / (1.f + __expf(-p.log_std[a])); }
 
-template <int MA, bool CONT>
+// Available_Continuous head (A <= 16: one logit tile, logits 0 and 1 in r = 0, 1 of the token's g = 0 lane): the
+// categorical over the two availability-masked logits 0, 1.  cls = argmax(act[:2]) (index 0 on a tie, as torch.argmax)
+struct AvCat { float lp[2], H; int cls; bool m[2]; };
+__device__ __forceinline__ AvCat av_cat(const DecP& p, const f32x4& L, size_t stok) {
+  AvCat s;
+  const float* arow = p.act + stok * p.A;
+  s.cls = arow[1] > arow[0] ? 1 : 0;
+  s.m[0] = p.ava && p.ava[stok * p.A] == 0.f;
+  s.m[1] = p.ava && p.ava[stok * p.A + 1] == 0.f;
+  const float l0 = s.m[0] ? -1e10f : L[0], l1 = s.m[1] ? -1e10f : L[1];
+  const float mx = fmaxf(l0, l1);
+  const float lse = mx + __logf(__expf(l0 - mx) + __expf(l1 - mx));
+  s.lp[0] = l0 - lse;
+  s.lp[1] = l1 - lse;
+  s.H = -(__expf(s.lp[0]) * s.lp[0] + __expf(s.lp[1]) * s.lp[1]);
+  return s;
+}
+
+template <int MA, bool CONT, bool AV = false>
 __device__ __forceinline__ void head_fwd_ct(const DecP& p, const CT* xr, bool save, const Ctx& c) {
   const int lane = c.lane, g = lane >> 4;
   HeadW<MA> W;
@@ -426,8 +464,8 @@ __device__ __forceinline__ void head_fwd_ct(const DecP& p, const CT* xr, bool sa
       const int row = rt * 16 + (lane & 15);
       const bool ok = row < c.NR;
       const size_t tok = (size_t)(c.tok0 + (ok ? row : 0)), stok = src_tok(p.sidx, tok, c.L);
-      const unsigned am = CONT ? 0u : slot_mask<MA>(p, stok, lane);
-      const float actf = CONT ? 0.f : p.act[stok];
+      const unsigned am = (CONT || AV) ? 0u : slot_mask<MA>(p, stok, lane);
+      const float actf = (CONT || AV) ? 0.f : p.act[stok];
       const CTr x = ct_pack(xr[k]);
       if (save) st_g(p.sv_head, c.tok0, rt, c.NR, x, lane);
       CT hh = bh, xh, n;
@@ -447,6 +485,25 @@ __device__ __forceinline__ void head_fwd_ct(const DecP& p, const CT* xr, bool sa
       f32x4 L[MA];
       head_logits_ct<MA>(p, W, n, L, lane);
       CP_MARK(33);
+      if (AV) {   // column 0: the availability choice; column a - 1: Normal(mean = logit a, std) of dimension a >= 2
+        static_assert(!AV || MA == 1, "Available_Continuous: one logit tile");
+        const int nlp = p.A - 1;
+        if (ok && g == 0) {
+          const AvCat s = av_cat(p, L[0], stok);
+          p.logp[tok * nlp] = s.cls ? s.lp[1] : s.lp[0];
+          p.ent[tok * nlp] = s.H;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int a = 4 * g + r;
+          if (ok && a >= 2 && a < p.A) {
+            const float sd = head_sd(p, a), z = (p.act[stok * p.A + a] - L[0][r]) / sd;
+            p.logp[tok * nlp + a - 1] = -0.5f * z * z - __logf(sd) - HALF_LOG_2PI;
+            p.ent[tok * nlp + a - 1] = 0.5f + HALF_LOG_2PI + __logf(sd);
+          }
+        }
+        continue;
+      }
       if (CONT) {   // per-dimension Normal(mean, std): this lane's dims a = 16ma + 4g + r
 #pragma unroll
         for (int ma = 0; ma < MA; ++ma)
@@ -493,7 +550,7 @@ __device__ __forceinline__ int small_wg_slot0(const DecP& p, int NB) {
   return (MDL_SMALL_WG_VACC && p.A <= 2 && s0 + 2 * p.A + 2 <= VSLOTS) ? s0 : -1;
 }
 
-template <int MA, bool CONT>
+template <int MA, bool CONT, bool AV = false>
 __device__ __forceinline__ void head_bwd_ct(const DecP& p, CT* dx, const Ctx& c, int vs0) {
   const int lane = c.lane, g = lane >> 4;
   constexpr int SB = (MA + 1) / 2;   // k-steps over the logit axis in dn = W_h2ᵀ dz
@@ -551,9 +608,9 @@ __device__ __forceinline__ void head_bwd_ct(const DecP& p, CT* dx, const Ctx& c,
         const int row = rt * 16 + (lane & 15);
         const bool ok = row < c.NR;
         const size_t tok = (size_t)(c.tok0 + (ok ? row : 0)), stok = src_tok(p.sidx, tok, c.L);
-        const unsigned am = CONT ? 0u : slot_mask<MA>(p, stok, lane);
-        const float actf = CONT ? 0.f : p.act[stok];
-        const float dlp = (ok && !CONT) ? p.dlogp[tok] : 0.f, den = (ok && !CONT) ? p.dent[tok] : 0.f;
+        const unsigned am = (CONT || AV) ? 0u : slot_mask<MA>(p, stok, lane);
+        const float actf = (CONT || AV) ? 0.f : p.act[stok];
+        const float dlp = (ok && !CONT && !AV) ? p.dlogp[tok] : 0.f, den = (ok && !CONT && !AV) ? p.dent[tok] : 0.f;
         const CT xh = ct_unpack(hxh[k]), ggp = ct_unpack(hgp[k]);
         const float rs = hrs[k];
         CT n;
@@ -561,14 +618,38 @@ __device__ __forceinline__ void head_bwd_ct(const DecP& p, CT* dx, const Ctx& c,
         for (int i = 0; i < 4; ++i) n.v[i] = xh.v[i] * gam.v[i] + bet.v[i];
         f32x4 L[MA];
         head_logits_ct<MA>(p, W, n, L, lane);
-        const bool disc = !CONT && (row % c.L) < p.n_disc;
+        const bool disc = !CONT && !AV && (row % c.L) < p.n_disc;
         const int act = min(max((int)actf, 0), p.A - 1);
-        const HeadStat st = CONT ? HeadStat{0.f, 0.f, 0.f, 0.f} : head_stats<MA>(p, L, am, act, disc, lane);
+        const HeadStat st = (CONT || AV) ? HeadStat{0.f, 0.f, 0.f, 0.f} : head_stats<MA>(p, L, am, act, disc, lane);
         // d loss / d logits of this lane's slots
         f32x4 Z[2 * SB];
 #pragma unroll
         for (int ma = 0; ma < 2 * SB; ++ma) Z[ma] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (CONT) {   // per-dimension Normal heads: d log p / d mean, and the log_std partials of this lane's dims
+        if (AV) {   // softmax gradient of the two masked logits (g = 0, r = 0, 1); Normal mean gradient of the rest
+          const int nlp = p.A - 1;
+          if (ok && g == 0) {
+            const AvCat s = av_cat(p, L[0], stok);
+            const float dl = p.dlogp[tok * nlp], de = p.dent[tok * nlp];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+              const float pr = __expf(s.lp[r]);
+              // a masked logit is a constant (masked_fill): no gradient reaches it
+              Z[0][r] = s.m[r] ? 0.f : dl * ((r == s.cls ? 1.f : 0.f) - pr) - de * pr * (s.lp[r] + s.H);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int a = 4 * g + r;
+            if (ok && a >= 2 && a < p.A) {
+              const float sd = head_sd(p, a), diff = p.act[stok * p.A + a] - L[0][r];
+              const float dl = p.dlogp[tok * nlp + a - 1], de = p.dent[tok * nlp + a - 1];
+              Z[0][r] = dl * diff / (sd * sd);
+              const float dsd = dl * (diff * diff / (sd * sd * sd) - 1.f / sd) + de / sd;
+              const float sg = 1.f / (1.f + __expf(-p.log_std[a]));
+              dlsv[0][r] += dsd * 0.5f * sg * (1.f - sg);   // dimensions 0, 1 stay exactly zero
+            }
+          }
+        } else if (CONT) {   // per-dimension Normal heads: d log p / d mean, and the log_std partials of this lane's dims
 #pragma unroll
           for (int ma = 0; ma < MA; ++ma)
 #pragma unroll
@@ -648,7 +729,7 @@ __device__ __forceinline__ void head_bwd_ct(const DecP& p, CT* dx, const Ctx& c,
   }
   flush_vec(dlg, c.g(p.lnh.dg), 0, c);
   flush_vec(dlb, c.g(p.lnh.db), 1, c);
-  if (CONT) {
+  if (CONT || AV) {   // (Available_Continuous: elements 0, 1 are added as zeros, so the flush stores them)
 #pragma unroll
     for (int ma = 0; ma < MA; ++ma)
 #pragma unroll
@@ -673,7 +754,7 @@ __device__ __forceinline__ void head_bwd_ct(const DecP& p, CT* dx, const Ctx& c,
 }
 
 // ============================================================================================== forward
-template <int NB, bool SAVE, int MA, bool CONT>
+template <int NB, bool SAVE, int MA, bool CONT, bool AV>
 __device__ __forceinline__ void dec_fwd_tile(const DecP& p, char* smem, int seq0, int nseq) {
   const Ctx c = make_ctx(p, smem, seq0, nseq);
   if (c.nseq <= 0) return;
@@ -682,7 +763,7 @@ __device__ __forceinline__ void dec_fwd_tile(const DecP& p, char* smem, int seq0
   CP_MARK(0);
   const int lane = c.lane;
   CT xr[MAXRT];
-  if (!CONT && emb_tab_fwd_ok(p)) {   // x0 rows from the per-token table (in QB until the first projection)
+  if (!CONT && !AV && emb_tab_fwd_ok(p)) {   // x0 rows from the per-token table (in QB until the first projection)
     float* X0 = (float*)c.QB;
     emb_table(p, X0, nullptr, nullptr, true, c);
     __syncthreads();
@@ -702,7 +783,7 @@ __device__ __forceinline__ void dec_fwd_tile(const DecP& p, char* smem, int seq0
       const int rt = c.wave + NW * k;
       if (rt < c.NT) {
         int tk;
-        CT pre = dec_embed_pre_ct<CONT>(p, rt, tk, c), xh;
+        CT pre = dec_embed_pre_ct<CONT, AV>(p, rt, tk, c), xh;
         gelu_ct(pre);
         ln_fwd_ct(pre, xh, xr[k], gam, bet);
       }
@@ -719,24 +800,24 @@ __device__ __forceinline__ void dec_fwd_tile(const DecP& p, char* smem, int seq0
                             p.sv[b].xh[1], p.sv[b].rs + 1 * (size_t)p.Bs * p.L, cc);
     mlp_fwd_ct<SAVE>(B.m[8], B.m[9], B.ln[2], xr, p.sv[b].x2, p.sv[b].g, p.sv[b].gp, p.sv[b].xh[2], p.sv[b].rs + 2 * (size_t)p.Bs * p.L, cc);
   }
-  head_fwd_ct<MA, CONT>(p, xr, SAVE, c);
+  head_fwd_ct<MA, CONT, AV>(p, xr, SAVE, c);
   CP_MARK(27);
 }
 
 #ifndef MDL_CT_BWD_TU
 // MA = logit tiles of the action head: 1 (A <= 16: DCML, MPE), 3 (A <= 48: SMAC's 36 actions) or 4 (A <= 64)
-template <int NB, bool SAVE, int MA, bool CONT>
+template <int NB, bool SAVE, int MA, bool CONT, bool AV = false>
 __global__ __launch_bounds__(NTHR, FWD_WGPC) void mat_dec_fwd_ct(DecP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   CP_BEGIN();
-  FOR_TILES(p, (dec_fwd_tile<NB, SAVE, MA, CONT>(p, smem, s0, ns)));
+  FOR_TILES(p, (dec_fwd_tile<NB, SAVE, MA, CONT, AV>(p, smem, s0, ns)));
   CP_END();
 }
 
 #endif  // !MDL_CT_BWD_TU
 
 // ============================================================================================== backward
-template <int NB, int MA, bool CONT>
+template <int NB, int MA, bool CONT, bool AV>
 __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0, int nseq, bool first) {
   const Ctx c = make_ctx(p, smem, seq0, nseq, first);
   if (c.nseq <= 0) return;
@@ -746,7 +827,7 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
   const int lane = c.lane;
   CT dx[MAXRT];
   const int vs0 = small_wg_slot0(p, NB);
-  head_bwd_ct<MA, CONT>(p, dx, c, vs0);
+  head_bwd_ct<MA, CONT, AV>(p, dx, c, vs0);
 #pragma unroll 1
   for (int bb = NB - 1; bb >= 0; --bb) {
     const Blk& B = p.blk[bb];
@@ -762,7 +843,7 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
                      p.sv[bb].rs + 0 * (size_t)p.Bs * p.L, true, cc, 5 + 6 * bb);
   }
   // ---------------- embedding backward: dW_a[:, token] += d pre ; LN_dec params
-  if (!CONT) {
+  if (!CONT && !AV) {
     // discrete tokens: dW_a (64 x (A+1)) = Σ_rows d pre ⊗ onehot(token) — a weight-gradient GEMM on MFMA with the
     // one-hot rows as X (wgrad_g), d pre as a hi/lo bf16 pair; replaces per-element LDS atomics that collided on
     // the (A+1) token rows (16-way address conflicts per wave instruction)
@@ -833,6 +914,11 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
     // atomic sums in LDS (fp32 atomicAdd from the 8 waves made the sum's order, and its last bits, vary by run)
     // opaque lane (as for the blocks): this phase's lane-derived addresses are otherwise computed at the kernel's start
     // and held, or spilled, across all of it
+    // Available_Continuous: dW_a (64 x (A+1)) = Σ_rows d pre ⊗ (start flag, a_prev), no bias — the same product with
+    // X column 0 = 1 on a sequence's first row and columns 1 .. A = the previous agent's action vector on the others
+    // (its one-hot head is exact in bf16; the continuous tail needs the lo tile).  A + 1 = 17 puts X column 16 into
+    // the second 16-column tile: XW column tiles are filled here, and wgrad_g walks ceil((A + 1) / 16) of them
+    constexpr int XW = AV ? 2 : MA;
     Ctx ce = c;
     asm volatile("" : "+v"(ce.lane), "+v"(ce.tid));
     const int lane = ce.lane, g = lane >> 4;
@@ -852,13 +938,15 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
         const int row = rt * 16 + (lane & 15);
         const bool has_prev = ok && row % ce.L != 0;
         const float* prev = p.act + (has_prev ? src_tok(p.sidx, (size_t)(ce.tok0 + row), ce.L) - 1 : 0) * p.A;
-        CT ap;   // a_prev in the feature slots: element 16 mt + 4 g + r (< A)
+        CT ap;   // a_prev in the feature slots: element 16 mt + 4 g + r (< A); Available_Continuous: shifted by one
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int a = 16 * mt + 4 * g + r;
-            ap.v[mt][r] = (mt < MA && has_prev && a < p.A) ? prev[a] : 0.f;
+            if (AV) ap.v[mt][r] = (mt < XW && a <= p.A) ? (a == 0 ? ((ok && !has_prev) ? 1.f : 0.f)
+                                                                  : (has_prev ? prev[a > 0 ? a - 1 : 0] : 0.f)) : 0.f;
+            else ap.v[mt][r] = (mt < XW && has_prev && a < p.A) ? prev[a] : 0.f;
           }
         CTr ah, al;
         ct_split(ap, ah, al);
@@ -872,7 +960,7 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
       if (rt < ce.NT) {
         const bool ok = tok_ok(rt, ce);
         int tk;
-        CT e = dec_embed_pre_ct<CONT>(p, rt, tk, ce), egp, xh, yy, de;
+        CT e = dec_embed_pre_ct<CONT, AV>(p, rt, tk, ce), egp, xh, yy, de;
         gelu_ct_both(e, egp);
         const float rs = ln_fwd_ct(e, xh, yy, gam, bet);
         ln_bwd_ct(dx[k], xh, rs, gam, ok, de, dlg, dlb);
@@ -889,7 +977,9 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
     flush_vec(dlg, ce.g(p.d_lnd_g), 2, ce);
     flush_vec(dlb, ce.g(p.d_lnd_b), 3, ce);
     __syncthreads();
-    if (p.d_wa || p.d_ba) {
+    if (AV) {   // W_a [64][A + 1] (row stride A + 1), no bias gradient; A >= 3: never the LDS slots
+      if (p.d_wa) wgrad_g(ce.DA, ce.XB, ce.KP, ce.g(p.d_wa), p.A + 1, 64, p.A + 1, nullptr, ce.wave, lane, ce.gm, ce.DQ, ce.QB);
+    } else if (p.d_wa || p.d_ba) {
       // W_a [64][A] (row stride A) and b_a: LDS slots vs0 .. vs0 + A - 1 and vs0 + A (the A + 1 slots the discrete
       // table takes), or one read-modify-write of a private copy per chunk
       if (vs0 >= 0) wgrad_g_vacc(ce.DA, ce.XB, ce.KP, ce.g(p.d_wa), p.A, 64, p.A, ce.g(p.d_ba), vs0, vs0 + p.A, ce, ce.DQ, ce.QB);
@@ -900,12 +990,12 @@ __device__ __forceinline__ void dec_bwd_tile(const DecP& p, char* smem, int seq0
 }
 
 #ifdef MDL_CT_BWD_TU
-template <int NB, int MA, bool CONT>
+template <int NB, int MA, bool CONT, bool AV = false>
 __global__ __launch_bounds__(NTHR, WGPC) void mat_dec_bwd_ct(DecP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   CP_BEGIN();
   vacc_begin(p, smem);
-  FOR_TILES(p, (dec_bwd_tile<NB, MA, CONT>(p, smem, s0, ns, it_ == 0)));
+  FOR_TILES(p, (dec_bwd_tile<NB, MA, CONT, AV>(p, smem, s0, ns, it_ == 0)));
   vacc_end(p, smem);
   CP_END();
 }
@@ -915,33 +1005,35 @@ __global__ __launch_bounds__(NTHR, WGPC) void mat_dec_bwd_ct(DecP p) {
 }  // namespace
 
 #ifndef MDL_CT_BWD_TU
-template <int MA, bool CONT>
+template <int MA, bool CONT, bool AV = false>
 static int dec_fwd_ct(const DecP* p, int NB, int save, hipStream_t st) {
-  if (NB == 1) return save ? launch_ct(mat_dec_fwd_ct<1, true, MA, CONT>, p, true, st) : launch_ct(mat_dec_fwd_ct<1, false, MA, CONT>, p, true, st);
-  if (NB == 2) return save ? launch_ct(mat_dec_fwd_ct<2, true, MA, CONT>, p, true, st) : launch_ct(mat_dec_fwd_ct<2, false, MA, CONT>, p, true, st);
-  if (NB == 3) return save ? launch_ct(mat_dec_fwd_ct<3, true, MA, CONT>, p, true, st) : launch_ct(mat_dec_fwd_ct<3, false, MA, CONT>, p, true, st);
+  if (NB == 1) return save ? launch_ct(mat_dec_fwd_ct<1, true, MA, CONT, AV>, p, true, st) : launch_ct(mat_dec_fwd_ct<1, false, MA, CONT, AV>, p, true, st);
+  if (NB == 2) return save ? launch_ct(mat_dec_fwd_ct<2, true, MA, CONT, AV>, p, true, st) : launch_ct(mat_dec_fwd_ct<2, false, MA, CONT, AV>, p, true, st);
+  if (NB == 3) return save ? launch_ct(mat_dec_fwd_ct<3, true, MA, CONT, AV>, p, true, st) : launch_ct(mat_dec_fwd_ct<3, false, MA, CONT, AV>, p, true, st);
   return -3;
 }
 // MA = logit tiles of the action head (1: A <= 16, 3: A <= 48 — SMAC's 36 actions, 4: A <= 64); the continuous
 // action type is its own instantiation (its Normal-head / Linear-embedding code kept out of the discrete kernels'
-// instruction stream)
+// instruction stream), and so is Available_Continuous (3 <= A <= 16: one logit tile)
 MDL_API int mdl_mat_dec_fwd_ct(const DecP* p, int NB, int save, hipStream_t st) {
   if (p->A > 64 || p->A < 1) return -1;
+  if (p->avail) return (p->cont || p->A < 3 || p->A > 16) ? -1 : dec_fwd_ct<1, false, true>(p, NB, save, st);
   if (p->cont) return p->A <= 16 ? dec_fwd_ct<1, true>(p, NB, save, st) : dec_fwd_ct<4, true>(p, NB, save, st);
   if (p->A <= 16) return dec_fwd_ct<1, false>(p, NB, save, st);
   return p->A <= 48 ? dec_fwd_ct<3, false>(p, NB, save, st) : dec_fwd_ct<4, false>(p, NB, save, st);
 }
 #else
-template <int MA, bool CONT>
+template <int MA, bool CONT, bool AV = false>
 static int dec_bwd_ct(const DecP* p, int NB, hipStream_t st) {
-  if (NB == 1) return launch_ct(mat_dec_bwd_ct<1, MA, CONT>, p, false, st);
-  if (NB == 2) return launch_ct(mat_dec_bwd_ct<2, MA, CONT>, p, false, st);
-  if (NB == 3) return launch_ct(mat_dec_bwd_ct<3, MA, CONT>, p, false, st);
+  if (NB == 1) return launch_ct(mat_dec_bwd_ct<1, MA, CONT, AV>, p, false, st);
+  if (NB == 2) return launch_ct(mat_dec_bwd_ct<2, MA, CONT, AV>, p, false, st);
+  if (NB == 3) return launch_ct(mat_dec_bwd_ct<3, MA, CONT, AV>, p, false, st);
   return -3;
 }
 
 MDL_API int mdl_mat_dec_bwd_ct(const DecP* p, int NB, hipStream_t st) {
   if (p->A > 64 || p->A < 1 || 2 * p->NRP * 128 < (p->A + 1) * 256) return -1;
+  if (p->avail) return (p->cont || p->A < 3 || p->A > 16) ? -1 : dec_bwd_ct<1, false, true>(p, NB, st);
   if (p->cont) return p->A <= 16 ? dec_bwd_ct<1, true>(p, NB, st) : dec_bwd_ct<4, true>(p, NB, st);
   if (p->A <= 16) return dec_bwd_ct<1, false>(p, NB, st);
   return p->A <= 48 ? dec_bwd_ct<3, false>(p, NB, st) : dec_bwd_ct<4, false>(p, NB, st);

@@ -125,6 +125,11 @@ struct DecP {
   // continuous action type (MA-MuJoCo, transformer_act.py:192-232): act / logp / ent / dlogp / dent are
   // [tok][A], the action embedding is Linear(A, 64) with bias (wa = [64][A], ba = [64]) on the previous agent's action
   int cont;
+  // Available_Continuous (transformer_act.py:234-322): act / ava are [tok][A] (act[:2] a one-hot of the availability
+  // choice, the rest Normal dimensions), logp / ent / dlogp / dent are [tok][A - 1] (column 0 the categorical over
+  // logits 0-1, column a - 1 the Normal of dimension a), the action embedding is Linear(A + 1, 64) without bias on
+  // (start flag, previous agent's action vector); 3 <= A <= 16
+  int avail;
   const float* ba;
   float* d_ba;
   HSv hs;                // action head (round 4)

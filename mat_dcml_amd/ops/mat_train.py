@@ -64,7 +64,8 @@ class DecP(ctypes.Structure):
                                   "ent")] + \
                [("sv", Sv * 3)] + [(n, VP) for n in ("dlogp", "dent", "drep", "sv_head")] + \
                [("g_delta", ctypes.c_longlong), ("g_stride", ctypes.c_longlong), ("g_copies", ctypes.c_int)] + \
-               [("cont", ctypes.c_int), ("ba", VP), ("d_ba", VP), ("hs", HSv), ("g_mode", ctypes.c_int), ("sidx", VP)]
+               [("cont", ctypes.c_int), ("avail", ctypes.c_int), ("ba", VP), ("d_ba", VP), ("hs", HSv),
+                ("g_mode", ctypes.c_int), ("sidx", VP)]
 
 
 # Training kernels (csrc/mat_train_ct.h): token-on-lane tiles, weight A fragments in permuted k order, register-
@@ -294,13 +295,36 @@ def encoder_unsupported_reasons(model):
     return r
 
 
+AVAIL_CONT_TYPES = ("Available_Continuous", "Available_Continous")
+AVAIL_CONT_ENV = "MAT_DCML_AVAIL_CONT_TRAIN"
+AVAIL_CONT_MIN_A, AVAIL_CONT_MAX_A = 3, 16   # one logit tile of the action head (csrc/mat_dec_ct.hip)
+
+
+def avail_cont_train_mode():
+    """How Available_Continuous models train, read from MAT_DCML_AVAIL_CONT_TRAIN at call time: ``hybrid`` (default:
+    fused encoder kernels under autograd, eager decoder) or ``fused`` (the Available_Continuous instantiation of the
+    fused decoder kernels: the whole update on HIP kernels, bit-reproducible)."""
+    mode = os.environ.get(AVAIL_CONT_ENV, "hybrid")
+    if mode not in ("hybrid", "fused"):
+        raise ValueError(f"{AVAIL_CONT_ENV}={mode}: expected 'hybrid' or 'fused'")
+    return mode
+
+
 def decoder_unsupported_reasons(model):
     dec = model.decoder
     r = _common_reasons(model)
     if dec.dec_actor:
         r.append("dec_actor")
     ok_types = ("Semi_Discrete", "Discrete", "Continuous", "Continous")
-    if model.action_type not in ok_types:
+    if model.action_type in AVAIL_CONT_TYPES:
+        # always named in full: the reason reads the same whichever spelling the action space used
+        if avail_cont_train_mode() != "fused":
+            r.append(f"action_type Available_Continuous trains through the hybrid path ({AVAIL_CONT_ENV}=fused selects "
+                     "the fused decoder kernels)")
+        elif not AVAIL_CONT_MIN_A <= model.action_dim <= AVAIL_CONT_MAX_A:
+            r.append(f"action_type Available_Continuous with action_dim {model.action_dim}: the fused decoder kernels "
+                     f"take {AVAIL_CONT_MIN_A} <= action_dim <= {AVAIL_CONT_MAX_A}")
+    elif model.action_type not in ok_types:
         r.append(f"action_type {model.action_type}")
     if model.action_dim > MAX_ACTION_DIM:
         r.append(f"action_dim {model.action_dim} > {MAX_ACTION_DIM}")
@@ -456,8 +480,11 @@ class DecoderFused:
         p = DecP()
         p.wa, p.d_wa = dec.action_encoder[0].weight.data_ptr(), _gptr(dec.action_encoder[0].weight)
         self.cont = m.action_type in ("Continuous", "Continous")
+        self.avail = m.action_type in AVAIL_CONT_TYPES
         if self.cont:   # Linear(A, 64) with bias on the previous agent's action vector
             p.cont, p.ba, p.d_ba = 1, dec.action_encoder[0].bias.data_ptr(), _gptr(dec.action_encoder[0].bias)
+        if self.avail:  # Linear(A + 1, 64) without bias on (start flag, previous agent's action vector): ba / d_ba null
+            p.avail = 1
         p.lnd_g, p.lnd_b, p.d_lnd_g, p.d_lnd_b = dec.ln.weight.data_ptr(), dec.ln.bias.data_ptr(), \
             _gptr(dec.ln.weight), _gptr(dec.ln.bias)
         for bi, blk in enumerate(dec.blocks):
@@ -484,7 +511,7 @@ class DecoderFused:
         m = self.model
         if m.action_type == "Discrete":
             return L
-        if m.action_type in ("Continuous", "Continous"):
+        if m.action_type in ("Continuous", "Continous") or m.action_type in AVAIL_CONT_TYPES:
             return 0
         return L + m.semi_index
 
@@ -503,10 +530,16 @@ class DecoderFused:
         dev = rep.device
         n_tok = B * L
         rep = rep.float().contiguous()
-        nlp = m.action_dim if self.cont else 1   # continuous: per-dimension actions / log-probs / entropies
+        A = m.action_dim
+        # stored-action width / log-prob and entropy width per token: continuous = per dimension; Available_Continuous
+        # = the A-wide action vector, and one categorical column plus A - 2 Normal columns
+        nact = A if (self.cont or self.avail) else 1
+        nlp = A if self.cont else A - 1 if self.avail else 1
         nrow = B if idx is None else actions.shape[0]
-        act = actions.reshape(nrow, L, nlp).float().contiguous()
+        act = actions.reshape(nrow, L, nact).float().contiguous()
         ava_c = ava.float().contiguous() if (ava is not None and not self.cont) else None
+        if self.avail and ava_c is not None and ava_c.numel() != nrow * L * A:
+            raise ValueError(f"available actions {tuple(ava.shape)}: expected ({nrow}, {L}, {A})")
         logp = torch.empty(B, L, nlp, device=dev)
         ent = torch.empty(B, L, nlp, device=dev)
         sfx = self._geom(B, L)
