@@ -991,7 +991,9 @@ __device__ __forceinline__ void attn_bwd_q_ct(const bf16_t* Q, const bf16_t* K, 
       d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, dsh, d1, 0, 0, 0);
       d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, dsl, d1, 0, 0, 0);
     }
-    st_lds_head(DQ, rt, h, d0 * ATT_SCALE, d1 * ATT_SCALE, q < c.NR, lane);
+    // L = 1: the softmax over one key is the constant 1, dS is exactly zero — the sums above hold dP - delta, the same
+    // products added in two orders, and a rounding-sized gradient still moves a weight by the full Adam step
+    st_lds_head(DQ, rt, h, d0 * ATT_SCALE, d1 * ATT_SCALE, q < c.NR && c.L != 1, lane);
   }
 }
 
@@ -1040,7 +1042,7 @@ __device__ __forceinline__ void attn_bwd_kv_ct(const bf16_t* Q, bf16_t* K, bf16_
       k1a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1, dsh, k1a, 0, 0, 0);
       k1a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1, dsl, k1a, 0, 0, 0);
     }
-    st_lds_head(K, rt, h, k0a * ATT_SCALE, k1a * ATT_SCALE, kv, lane);
+    st_lds_head(K, rt, h, k0a * ATT_SCALE, k1a * ATT_SCALE, kv && c.L != 1, lane);   // L = 1: dS = 0 (attn_bwd_q_ct)
     st_lds_head(V, rt, h, v0a, v1a, kv, lane);
   }
 }
