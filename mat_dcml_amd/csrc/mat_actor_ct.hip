@@ -1,0 +1,260 @@
+// Fused MAT-Dec shared actor forward / backward, token-on-lane tiles (mat_train_ct.h).  Reference:
+// ma_transformer.py:181-188,212-216 (Decoder with dec_actor and share_actor: one MLP on every agent's observation),
+// transformer_act.py:103-129,176-189 (log-prob / entropy of the stored actions).
+//
+// The actor is two stages the training kernels already hold, run back to back on one token tile with no attention, no
+// cross attention and no LDS in the forward:
+//  * LN(od) -> Linear(od, 64) -> GELU -> LN: the encoder's observation embedding and its ln (mat_enc_ct.hip obs_ln /
+//    we_frags / embed_pre / ln_fwd_ct; backward: the embedding part of enc_bwd_tile);
+//  * Linear(64, 64) -> GELU -> LN -> Linear(64, A) + the categorical / Normal statistics and masks: the decoder's
+//    action head (mat_dec_ct.hip head_fwd_ct / head_bwd_ct).
+// Both files are included for their device functions only (MDL_CT_NO_API); the kernel argument ActP is viewed as the
+// EncP / DecP fields those functions read (locals that never leave registers: the unused fields fold away).
+// The backward runs on the persistent grid of the other training backwards (launch_ct, chunk plan and stagger of
+// FOR_TILES), so a minibatch's backwards all write the same mdl_ct_bwd_grid(B, SQ) private gradient copies.
+#define MDL_CT_NO_API
+#include "mat_enc_ct.hip"
+#include "mat_dec_ct.hip"
+
+namespace {
+
+__device__ __forceinline__ EncP actor_enc_view(const ActP& a) {
+  EncP p = {};
+  p.Bs = a.Bs; p.L = a.L; p.od = a.od; p.SQ = a.SQ; p.NRP = a.NRP; p.n_obj = 1;
+  p.obs = a.obs;
+  p.lno_g = a.lno_g; p.lno_b = a.lno_b; p.we = a.we; p.be = a.be; p.ln0_g = a.ln0_g; p.ln0_b = a.ln0_b;
+  p.d_lno_g = a.d_lno_g; p.d_lno_b = a.d_lno_b; p.d_we = a.d_we; p.d_be = a.d_be;
+  p.d_ln0_g = a.d_ln0_g; p.d_ln0_b = a.d_ln0_b;
+  p.es = a.es;
+  p.g_delta = a.g_delta; p.g_stride = a.g_stride; p.g_copies = a.g_copies; p.g_mode = a.g_mode;
+  p.sidx = a.sidx;
+  return p;
+}
+
+__device__ __forceinline__ DecP actor_dec_view(const ActP& a) {
+  DecP p = {};
+  p.Bs = a.Bs; p.L = a.L; p.A = a.A; p.SQ = a.SQ; p.NRP = a.NRP; p.n_disc = a.n_disc;
+  p.act = a.act; p.ava = a.ava;
+  p.h1 = a.h1; p.lnh = a.lnh;
+  p.wh2 = a.wh2; p.bh2 = a.bh2; p.d_wh2 = a.d_wh2; p.d_bh2 = a.d_bh2;
+  p.log_std = a.log_std; p.d_log_std = a.d_log_std;
+  p.logp = a.logp; p.ent = a.ent; p.dlogp = a.dlogp; p.dent = a.dent;
+  p.sv_head = a.sv_head; p.hs = a.hs;
+  p.g_delta = a.g_delta; p.g_stride = a.g_stride; p.g_copies = a.g_copies; p.g_mode = a.g_mode;
+  p.cont = a.cont;
+  p.sidx = a.sidx;
+  return p;
+}
+
+// ============================================================================================== forward
+// LOGITS (rollout, never with SAVE): the head's unmasked logits [tok][A] leave instead of log-prob / entropy — the
+// same embedding, W_2, LayerNorm and logit products as the learner's pass; masking and sampling stay with the caller
+template <bool SAVE, int MA, bool CONT, bool LOGITS>
+__device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, const DecP& pd, char* smem, int seq0,
+                                               int nseq) {
+  const Ctx c = make_ctx(a, smem, seq0, nseq);
+  if (c.nseq <= 0) return;
+  const int lane = c.lane, g = lane >> 4;
+  const EncX ex{nullptr, nullptr};
+  CT xr[MAXRT];
+  {
+    bf16x8 W[4];
+    we_frags(pe, W, lane);
+    const CT gam = ld_vec(pe.ln0_g, lane), bet = ld_vec(pe.ln0_b, lane);
+#pragma unroll
+    for (int k = 0; k < MAXRT; ++k) {
+      const int rt = c.wave + NW * k;
+      if (rt < c.NT) {
+        float oh[4], hat[4];
+        CT pre = embed_pre(pe, ex, rt, W, oh, hat, c), xh;
+        if (SAVE) {   // x-hat, GELU'(pre), rstd for the backward (which recomputes none of the embedding forward)
+          CT gp;
+          gelu_ct_both(pre, gp);
+          const float rs = ln_fwd_ct(pre, xh, xr[k], gam, bet);
+          st_g(pe.es.xh, c.tok0, rt, c.NR, ct_pack(xh), lane);
+          st_g(pe.es.gp, c.tok0, rt, c.NR, ct_pack(gp), lane);
+          st_tokf(pe.es.rs, rt, rs, c);
+        } else {
+          gelu_ct(pre);
+          ln_fwd_ct(pre, xh, xr[k], gam, bet);
+        }
+      }
+    }
+  }
+  if (!LOGITS) {
+    head_fwd_ct<MA, CONT, false>(pd, xr, SAVE, c);
+    return;
+  }
+  HeadW<MA> W;
+  head_w<MA>(pd, W, lane);
+  AFr H;
+  loadA(H, pd.h1.fa, lane);
+  const CT bh = ld_vec(pd.h1.b, lane), gam = ld_vec(pd.lnh.g, lane), bet = ld_vec(pd.lnh.b, lane);
+#pragma unroll
+  for (int k = 0; k < MAXRT; ++k) {
+    const int rt = c.wave + NW * k;
+    if (rt < c.NT) {
+      const int row = rt * 16 + (lane & 15);
+      const bool ok = row < c.NR;
+      const size_t tok = (size_t)(c.tok0 + (ok ? row : 0));
+      CT hh = bh, xh, n;
+      mm(hh, H, ct_pack(xr[k]));
+      gelu_ct(hh);
+      ln_fwd_ct(hh, xh, n, gam, bet);
+      f32x4 L[MA];
+      head_logits_ct<MA>(pd, W, n, L, lane);
+#pragma unroll
+      for (int ma = 0; ma < MA; ++ma)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = 16 * ma + 4 * g + r;
+          if (ok && i < a.A) a.logits[tok * a.A + i] = L[ma][r];
+        }
+    }
+  }
+}
+
+#ifndef MDL_CT_BWD_TU
+template <bool SAVE, int MA, bool CONT, bool LOGITS>
+__global__ __launch_bounds__(NTHR, FWD_WGPC) void mat_actor_fwd_ct(ActP a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const EncP pe = actor_enc_view(a);
+  const DecP pd = actor_dec_view(a);
+  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS>(a, pe, pd, smem, s0, ns)));
+}
+#endif  // !MDL_CT_BWD_TU
+
+// ============================================================================================== backward
+// LDS vector slots: 0-1 head LayerNorm, 4 log_std (head_bwd_ct), 5-6 embedding LayerNorm, 7 embedding bias, 8-9
+// observation LayerNorm (as enc_bwd_tile), 10 .. 10 + A - 1 the rows of d W_h2 and 10 + A d b_h2 for A <= 2 (head_bwd_ct
+// places them at vs0 + A + 1 ..: vs0 = 9 - A); a wider head flushes d W_h2 per chunk (private copy / atomics)
+__device__ __forceinline__ int actor_small_wg_slot0(const ActP& a) {
+  return (MDL_SMALL_WG_VACC && a.A <= 2 && 10 + a.A + 1 <= VSLOTS) ? 9 - a.A : -1;
+}
+
+template <int MA, bool CONT>
+__device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, const DecP& pd, char* smem, int seq0,
+                                               int nseq, bool first) {
+  const Ctx c = make_ctx(a, smem, seq0, nseq, first);
+  if (c.nseq <= 0) return;
+  zero_pad_rows(c);
+  __syncthreads();
+  const int lane = c.lane;
+  CT dx[MAXRT];
+  // ---------------- head backward: dx = d LN0 output; d W_2, d W_h2, their biases, the head LayerNorm, log_std
+  head_bwd_ct<MA, CONT, false>(pd, dx, c, actor_small_wg_slot0(a));
+  // ---------------- embedding backward: x0 = LN0(GELU(pre)), pre = W_1 · LN_obs(obs) + b_1  (enc_bwd_tile)
+  {
+    CT dlg, dlb, dbe;
+    ct_zero(dlg);
+    ct_zero(dlb);
+    ct_zero(dbe);
+    f32x4 dog = {0.f, 0.f, 0.f, 0.f}, dob = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 WT[2];
+    weT_frags(p, WT, lane);
+    const CT gam = ld_vec(p.ln0_g, lane);
+#pragma unroll
+    for (int k = 0; k < MAXRT; ++k) {
+      const int rt = c.wave + NW * k;
+      if (rt < c.NT) {
+        const bool ok = tok_ok(rt, c);
+        float oh[4] = {0.f, 0.f, 0.f, 0.f}, hat[4] = {0.f, 0.f, 0.f, 0.f};
+        obs_ln(p, rt, c, oh, hat);   // X of W_1 and the LN_obs backward (od <= 16 dims in-lane)
+        // the forward's x-hat, GELU'(pre) and rstd (no embedding product, GELU or LayerNorm forward here)
+        const CT xh = ct_unpack(ld_g(p.es.xh, c.tok0, rt, c.NR, lane)), egp = ct_unpack(ld_g(p.es.gp, c.tok0, rt, c.NR, lane));
+        CT de;
+        ln_bwd_ct(dx[k], xh, ld_tokf(p.es.rs, rt, c), gam, ok, de, dlg, dlb);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) de.v[i] *= egp.v[i];   // padded rows: zero
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dbe.v[i] += de.v[i];
+        CTr dh, dl;
+        ct_split(de, dh, dl);
+        st_lds(c.DA, rt, dh, ok, lane);   // dY of W_1
+        CTr xo = ct_zero_r();
+        xo.q[0] = make_uint2(pk2(oh[0], oh[1]), pk2(oh[2], oh[3]));
+        st_lds(c.XB, rt, xo, ok, lane);   // X of W_1 (obs dims 0..15 = features 0..15 of the LDS row)
+        // d(LN_obs output)[dim 4g + r] of this lane's token
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WT[s], rb(dh, s), d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WT[s], rb(dl, s), d, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          dog[r] += ok ? d[r] * hat[r] : 0.f;
+          dob[r] += ok ? d[r] : 0.f;
+        }
+      }
+    }
+    flush_vec(dlg, c.g(p.d_ln0_g), 5, c);
+    flush_vec(dlb, c.g(p.d_ln0_b), 6, c);
+    flush_vec(dbe, c.g(p.d_be), 7, c);
+    const int c16 = lane & 15, g = lane >> 4;
+    float og = 0.f, ob = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float s0 = group_sum<16>(dog[r]), s1 = group_sum<16>(dob[r]);
+      og = c16 == r ? s0 : og;
+      ob = c16 == r ? s1 : ob;
+    }
+    const int dim = 4 * g + c16;
+    if (c16 < 4 && dim < p.od) {
+      if (p.d_lno_g) vacc_add(c.g(p.d_lno_g), 8, dim, og, c, p.od);
+      if (p.d_lno_b) vacc_add(c.g(p.d_lno_b), 9, dim, ob, c, p.od);
+    }
+    __syncthreads();
+    wgrad_g(c.DA, c.XB, c.KP, c.g(p.d_we), p.od, 64, p.od, nullptr, c.wave, lane, c.gm);
+  }
+}
+
+#ifdef MDL_CT_BWD_TU
+template <int MA, bool CONT>
+__global__ __launch_bounds__(NTHR, WGPC) void mat_actor_bwd_ct(ActP a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const EncP pe = actor_enc_view(a);
+  const DecP pd = actor_dec_view(a);
+  vacc_begin(a, smem);
+  FOR_TILES(a, (actor_bwd_tile<MA, CONT>(a, pe, pd, smem, s0, ns, it_ == 0)));
+  vacc_end(a, smem);
+}
+#endif  // MDL_CT_BWD_TU
+
+}  // namespace
+
+// ============================================================================================== host API
+static bool actor_args_ok(const ActP* p) {
+  return p->od >= 1 && p->od <= 16 && p->A >= 1 && p->A <= 64 && p->n_disc >= 0 && p->n_disc <= p->L &&
+         !(p->cont && p->n_disc != 0);
+}
+
+#ifndef MDL_CT_BWD_TU
+template <int MA, bool CONT>
+static int actor_fwd_ct(const ActP* p, int save, hipStream_t st) {
+  return save ? launch_ct(mat_actor_fwd_ct<true, MA, CONT, false>, p, true, st)
+              : launch_ct(mat_actor_fwd_ct<false, MA, CONT, false>, p, true, st);
+}
+// MA = logit tiles of the head as in mdl_mat_dec_fwd_ct.  p->logits (no save): the logits-only pass of the rollout,
+// which needs neither stored actions nor availability
+MDL_API int mdl_mat_actor_fwd_ct(const ActP* p, int save, hipStream_t st) {
+  if (!actor_args_ok(p)) return -1;
+  if (p->logits) {
+    if (save) return -1;
+    if (p->A <= 16) return launch_ct(mat_actor_fwd_ct<false, 1, false, true>, p, true, st);
+    return p->A <= 48 ? launch_ct(mat_actor_fwd_ct<false, 3, false, true>, p, true, st)
+                      : launch_ct(mat_actor_fwd_ct<false, 4, false, true>, p, true, st);
+  }
+  if (!p->act || !p->logp || !p->ent) return -1;
+  if (p->cont) return p->A <= 16 ? actor_fwd_ct<1, true>(p, save, st) : actor_fwd_ct<4, true>(p, save, st);
+  if (p->A <= 16) return actor_fwd_ct<1, false>(p, save, st);
+  return p->A <= 48 ? actor_fwd_ct<3, false>(p, save, st) : actor_fwd_ct<4, false>(p, save, st);
+}
+#else
+MDL_API int mdl_mat_actor_bwd_ct(const ActP* p, hipStream_t st) {
+  if (!actor_args_ok(p) || !p->act || !p->dlogp || !p->dent || !p->sv_head || !p->hs.xh || !p->es.xh) return -1;
+  if (p->cont) return p->A <= 16 ? launch_ct(mat_actor_bwd_ct<1, true>, p, false, st) : launch_ct(mat_actor_bwd_ct<4, true>, p, false, st);
+  if (p->A <= 16) return launch_ct(mat_actor_bwd_ct<1, false>, p, false, st);
+  return p->A <= 48 ? launch_ct(mat_actor_bwd_ct<3, false>, p, false, st) : launch_ct(mat_actor_bwd_ct<4, false>, p, false, st);
+}
+#endif  // MDL_CT_BWD_TU

@@ -1004,6 +1004,8 @@ __global__ __launch_bounds__(NTHR, WGPC) void mat_dec_bwd_ct(DecP p) {
 
 }  // namespace
 
+// (MDL_CT_NO_API: a translation unit that only composes this file's device functions, mat_actor_ct.hip)
+#ifndef MDL_CT_NO_API
 #ifndef MDL_CT_BWD_TU
 template <int MA, bool CONT, bool AV = false>
 static int dec_fwd_ct(const DecP* p, int NB, int save, hipStream_t st) {
@@ -1049,3 +1051,4 @@ MDL_API int MDL_CAT(mdl_ctprof_dec, MDL_CT_TU_SUFFIX)(unsigned long long* out, i
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ctprof), sizeof(unsigned long long) * 64, 0, hipMemcpyDeviceToHost);
 }
 #endif
+#endif  // !MDL_CT_NO_API

@@ -397,6 +397,8 @@ __global__ __launch_bounds__(NTHR, WGPC) void mat_enc_bwd_ct(EncP p, EncX ex) {
 }  // namespace
 
 // ============================================================================================== host API
+// (MDL_CT_NO_API: a translation unit that only composes this file's device functions, mat_actor_ct.hip)
+#ifndef MDL_CT_NO_API
 #ifndef MDL_CT_BWD_TU
 MDL_API int mdl_mat_train_geometry_ct(int L) {
   const int MAXROWS = 16 * NW * MAXRT;   // row tiles of one round of the forward's waves
@@ -448,3 +450,4 @@ MDL_API int MDL_CAT(mdl_ctprof_enc, MDL_CT_TU_SUFFIX)(unsigned long long* out, i
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ctprof), sizeof(unsigned long long) * 64, 0, hipMemcpyDeviceToHost);
 }
 #endif
+#endif  // !MDL_CT_NO_API

@@ -137,6 +137,38 @@ struct DecP {
   const long long* sidx; // minibatch sequence -> rollout-buffer sequence of `act` / `ava` (null: dense)
 };
 
+// MAT-Dec's shared actor (models/mat.py Decoder with dec_actor and share_actor; mat_actor_ct.hip): LN(od) ->
+// Linear(od, 64) -> GELU -> LN -> Linear(64, 64) -> GELU -> LN -> Linear(64, A) on the observations alone.  The first
+// four modules take the encoder embedding's fields (EncP: lno, we / be, ln0, es), the last four the action head's
+// (DecP: h1, lnh, wh2 / bh2, log_std, hs, sv_head = the head's input); act / ava / logp / ent / dlogp / dent as in DecP
+// (cont: [tok][A] per dimension).  logits (forward without save, optional): [tok][A] f32, the unmasked head output.
+struct ActP {
+  int Bs, L, od, A, SQ, NRP, n_disc, cont;
+  const float* obs;
+  const float* act;
+  const float* ava;
+  const float *lno_g, *lno_b, *we, *be, *ln0_g, *ln0_b;
+  float *d_lno_g, *d_lno_b, *d_we, *d_be, *d_ln0_g, *d_ln0_b;
+  Mat h1;
+  LNp lnh;
+  const float* wh2;
+  const float* bh2;
+  float* d_wh2;
+  float* d_bh2;
+  const float* log_std;
+  float* d_log_std;
+  float* logp;
+  float* ent;
+  float* logits;
+  const float* dlogp;
+  const float* dent;
+  bf16_t* sv_head;
+  HSv hs, es;
+  long long g_delta, g_stride;
+  int g_copies, g_mode;
+  const long long* sidx;   // minibatch sequence -> rollout-buffer sequence of obs / act / ava (null: dense)
+};
+
 // Round 6: the training kernels read the minibatch's INPUTS (observations, stored actions, availability) straight
 // from the rollout buffer through the epoch permutation (sidx), so no gather copy precedes them; token tok of the
 // dense minibatch order (outputs, saved activations, loss gradients) reads input row src_tok(tok).

@@ -67,14 +67,23 @@ def unsupported_reasons(model, L=None) -> list:
     if _is_avail_cont(model) and model.action_dim < 3:
         r.append(f"Available_Continuous with action_dim {model.action_dim} < 3")
     if model.decoder.dec_actor:
-        r.append("dec_actor (mat_dec) has no autoregressive decode")
+        # MAT-Dec has no autoregressive decode: its rollout is one actor pass.  With MAT_DCML_DEC_ACTOR_TRAIN=fused and
+        # a model inside the fused actor kernels' gates that pass is csrc/mat_actor_ct.hip (get_actions below);
+        # otherwise the eager actor (the reasons name the switch or the limit)
+        from . import mat_train
+        why = mat_train.dec_actor_reasons(model)
+        if why:
+            r.append("dec_actor (mat_dec) has no autoregressive decode")
+            r += why
+        elif mat_train.geometry(L or model.n_agent)[0] <= 0:
+            r.append(f"L={L or model.n_agent} does not fit the training tiling")
     if model.n_embd != 64 or model.n_head != 2 or model.n_block not in (1, 2, 3):
         r.append(f"n_embd {model.n_embd} / n_head {model.n_head} / n_block {model.n_block} (kernel: 64 / 2 / 1-3)")
     if model.action_dim > 64:
         r.append(f"action_dim {model.action_dim} > 64")
     if model.action_type == "Semi_Discrete" and model.semi_index != -1:
         r.append(f"semi_index {model.semi_index} != -1")
-    if not r and lib().mdl_mat_decode_geometry(model.n_block, L or model.n_agent, 1) <= 0:
+    if not r and not model.decoder.dec_actor and lib().mdl_mat_decode_geometry(model.n_block, L or model.n_agent, 1) <= 0:
         r.append(f"L={L or model.n_agent} does not fit the decode kernel's LDS")
     return r
 
@@ -182,7 +191,7 @@ def refresh_packs(model):
     from . import mat_train
     if not next(model.parameters()).is_cuda or kernels.mode() == "torch":
         return
-    if supports(model):
+    if supports(model) and not model.decoder.dec_actor:   # (MAT-Dec: the actor's one matrix is in the ModelPack)
         decoder_pack(model)
     if mat_train.encoder_supported(model):
         enc, _, _ = mat_train._state(model, next(model.parameters()).device)
@@ -311,8 +320,33 @@ def _encode(model, obs):
 @torch.no_grad()
 def get_actions(model, obs, ava=None, deterministic=False, stride=1, rand=None):
     v, rep = _encode(model, obs)
+    if model.decoder.dec_actor:
+        return (v,) + _actor_act(model, obs, ava, deterministic, rand)
     a, lp = decode(model, rep, ava, deterministic, stride, rand)
     return v, a, lp
+
+
+def _actor_act(model, obs, ava, deterministic, rand):
+    """MAT-Dec rollout step on the fused actor kernel: logits from ``mat_actor_fwd_ct`` (the arithmetic the learner's
+    pass evaluates), then the heads of the eager path on the caller's draws — or, without them, the Philox-keyed draws
+    ``policy.get_actions`` makes for the eager actor (``set_sampling_key``), else torch's generator."""
+    from . import mat_train
+    from ..models import act as act_mod
+    B, L = obs.shape[0], obs.shape[1]
+    A = model.action_dim
+    _, actor, _ = mat_train._state(model, obs.device)
+    logits = actor.logits(obs)
+    if rand is None and not deterministic:
+        if getattr(model, "_mdl_env0", None) is not None:
+            k0, k1, c = next_draw_key(model)
+            rand = act_mod.philox_rand(B, L, A, k0, k1, c, model._mdl_env0, obs.device,
+                                       normal=model.action_type != "Discrete")
+        else:
+            rand = act_mod.make_rand(B, L, A, obs.device)
+    if rand is None:
+        rand = {"u": torch.zeros(B, L, device=obs.device), "n": torch.zeros(B, L, A, device=obs.device)}
+    std = model.action_std() if model.action_type != "Discrete" else None
+    return act_mod._heads_from_logits(model, logits, ava, deterministic, rand, act_mod.n_discrete_agents(model, L), std)
 
 
 @torch.no_grad()

@@ -6,6 +6,8 @@
 * ``EncoderFused`` / ``DecoderFused`` — the whole-encoder / whole-decoder (teacher-forced) forward with the
   activations the backward needs, and the backward, which writes parameter gradients straight into ``.grad``
   (fp32 atomics; the grads are views of one flat buffer, see ``parallel/comm.FlatGrads``).
+* ``ActorFused`` — MAT-Dec's shared actor (``dec_actor``) behind DecoderFused's interface (``csrc/mat_actor_ct.hip``),
+  selected by ``MAT_DCML_DEC_ACTOR_TRAIN=fused``.
 * ``evaluate_actions`` — autograd entry used by the PPO trainer: (values, log-probs, entropy) of stored actions.
 """
 from __future__ import annotations
@@ -68,6 +70,17 @@ class DecP(ctypes.Structure):
                 ("g_mode", ctypes.c_int), ("sidx", VP)]
 
 
+class ActP(ctypes.Structure):   # csrc/mat_train_common.h ActP: MAT-Dec's shared actor (csrc/mat_actor_ct.hip)
+    _fields_ = [(n, ctypes.c_int) for n in ("Bs", "L", "od", "A", "SQ", "NRP", "n_disc", "cont")] + \
+               [(n, VP) for n in ("obs", "act", "ava", "lno_g", "lno_b", "we", "be", "ln0_g", "ln0_b", "d_lno_g",
+                                  "d_lno_b", "d_we", "d_be", "d_ln0_g", "d_ln0_b")] + \
+               [("h1", Mat), ("lnh", LNp)] + \
+               [(n, VP) for n in ("wh2", "bh2", "d_wh2", "d_bh2", "log_std", "d_log_std", "logp", "ent", "logits",
+                                  "dlogp", "dent", "sv_head")] + \
+               [("hs", HSv), ("es", HSv), ("g_delta", ctypes.c_longlong), ("g_stride", ctypes.c_longlong),
+                ("g_copies", ctypes.c_int), ("g_mode", ctypes.c_int), ("sidx", VP)]
+
+
 # Training kernels (csrc/mat_train_ct.h): token-on-lane tiles, weight A fragments in permuted k order, register-
 # chained linears.  The forward kernels run 4 waves x 2 workgroups per CU, the backward 8 waves x 1 (its own
 # translation units); the tile geometry comes from mdl_mat_train_geometry_ct.
@@ -76,6 +89,8 @@ sig("mdl_mat_enc_fwd_ct", ctypes.POINTER(EncP), VP, ctypes.c_int, ctypes.c_int, 
 sig("mdl_mat_enc_bwd_ct", ctypes.POINTER(EncP), VP, VP, ctypes.c_int, VP)
 sig("mdl_mat_dec_fwd_ct", ctypes.POINTER(DecP), ctypes.c_int, ctypes.c_int, VP)
 sig("mdl_mat_dec_bwd_ct", ctypes.POINTER(DecP), ctypes.c_int, VP)
+sig("mdl_mat_actor_fwd_ct", ctypes.POINTER(ActP), ctypes.c_int, VP)
+sig("mdl_mat_actor_bwd_ct", ctypes.POINTER(ActP), VP)
 sig("mdl_grad_reduce", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP)
 sig("mdl_grad_reduce_norm", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP, VP)
 sig("mdl_grad_reduce_priv", VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, VP, VP)
@@ -202,8 +217,8 @@ def _gptr(t):
 def decoder_linears(model):
     dec = model.decoder
     out = []
-    if dec.dec_actor:   # MAT-Dec: per-agent MLP actors, no transformer blocks to pack (hybrid path: eager decoder)
-        return out
+    if dec.dec_actor:   # MAT-Dec: no transformer blocks to pack; a shared actor's Linear(64, 64) is the one 64 x 64
+        return [dec.mlp[4]] if dec.share_actor else out   # matrix the fused actor kernels read as fragments
     for blk in dec.blocks:
         a1, a2 = blk.attn1, blk.attn2
         out += [a1.query, a1.key, a1.value, a1.proj, a2.query, a2.key, a2.value, a2.proj, blk.mlp[0], blk.mlp[2]]
@@ -310,13 +325,52 @@ def avail_cont_train_mode():
     return mode
 
 
+DEC_ACTOR_ENV = "MAT_DCML_DEC_ACTOR_TRAIN"
+
+
+def dec_actor_train_mode():
+    """How MAT-Dec (``dec_actor``) models train and roll out, read from MAT_DCML_DEC_ACTOR_TRAIN at call time:
+    ``hybrid`` (default: fused encoder kernels under autograd, eager actor) or ``fused`` (csrc/mat_actor_ct.hip: the
+    shared actor's forward / backward kernels — the whole update on HIP kernels, bit-reproducible)."""
+    mode = os.environ.get(DEC_ACTOR_ENV, "hybrid")
+    if mode not in ("hybrid", "fused"):
+        raise ValueError(f"{DEC_ACTOR_ENV}={mode}: expected 'hybrid' or 'fused'")
+    return mode
+
+
+def dec_actor_reasons(model):
+    """Why a ``dec_actor`` model stays off the fused actor kernels: the switch, or one reason per condition they set
+    beyond the shared gates (action_dim <= 64, semi_index == -1, the tiling)."""
+    dec = model.decoder
+    if dec_actor_train_mode() != "fused":
+        return [f"dec_actor (MAT-Dec) trains through the hybrid path ({DEC_ACTOR_ENV}=fused selects the fused actor "
+                "kernels)"]
+    r = []
+    if not dec.share_actor:
+        r.append(f"dec_actor with per-agent actors (share_actor=False): {DEC_ACTOR_ENV}=fused takes the shared actor")
+    if model.encoder.obs_dim > MAX_FUSED_OBS:
+        r.append(f"dec_actor with obs_dim {model.encoder.obs_dim} > {MAX_FUSED_OBS}: the fused actor kernels embed "
+                 f"at most {MAX_FUSED_OBS} observation features")
+    if model.action_type in AVAIL_CONT_TYPES:
+        r.append("dec_actor with action_type Available_Continuous: the fused actor kernels take Discrete, "
+                 "Semi_Discrete and Continuous")
+    return r
+
+
+def dec_actor_fused(model):
+    """A MAT-Dec model whose actor runs on the fused actor kernels (switch set, every gate open)."""
+    return bool(model.decoder.dec_actor) and not decoder_unsupported_reasons(model)
+
+
 def decoder_unsupported_reasons(model):
     dec = model.decoder
     r = _common_reasons(model)
     if dec.dec_actor:
-        r.append("dec_actor")
+        r += dec_actor_reasons(model)
     ok_types = ("Semi_Discrete", "Discrete", "Continuous", "Continous")
-    if model.action_type in AVAIL_CONT_TYPES:
+    if dec.dec_actor and model.action_type in AVAIL_CONT_TYPES:
+        pass   # named above (no actor instantiation takes it, whatever MAT_DCML_AVAIL_CONT_TRAIN says)
+    elif model.action_type in AVAIL_CONT_TYPES:
         # always named in full: the reason reads the same whichever spelling the action space used
         if avail_cont_train_mode() != "fused":
             r.append(f"action_type Available_Continuous trains through the hybrid path ({AVAIL_CONT_ENV}=fused selects "
@@ -589,6 +643,155 @@ class DecoderFused:
         return drep
 
 
+# ------------------------------------------------------------------------------------------------- MAT-Dec actor
+class ActorFused:
+    """MAT-Dec's shared actor (``decoder.mlp``: LN(od) -> Linear(od, 64) -> GELU -> LN -> Linear(64, 64) -> GELU -> LN ->
+    Linear(64, A)) on csrc/mat_actor_ct.hip, with DecoderFused's interface.  The actor reads the observations, not
+    ``rep``: ``obs`` defaults to what ``enc`` (the model's EncoderFused) read in its last forward — the same rows, dense
+    or through the same ``idx`` — and the backward's d rep is a cached zero tensor."""
+
+    def __init__(self, model, enc=None):
+        self.model = model
+        self.enc = enc
+        self.p = None
+        self.sig = None
+        self.ctx = None
+        self._zero = None
+
+    def _build(self):
+        m = self.model
+        s = _grad_sig(m)
+        if self.p is not None and self.sig == s:
+            return
+        dec = m.decoder
+        if not (dec.dec_actor and dec.share_actor):
+            raise RuntimeError("ActorFused: the model has no shared actor (dec_actor and share_actor)")
+        mp = model_pack(m)
+        a = dec.mlp
+        p = ActP()
+        for name, t in (("lno_g", a[0].weight), ("lno_b", a[0].bias), ("we", a[1].weight), ("be", a[1].bias),
+                        ("ln0_g", a[3].weight), ("ln0_b", a[3].bias)):
+            setattr(p, name, t.data_ptr())
+            setattr(p, "d_" + name, _gptr(t))
+        p.h1 = mp.mat(a[4])
+        p.lnh = _ln(a[6])
+        p.wh2, p.bh2, p.d_wh2, p.d_bh2 = a[7].weight.data_ptr(), a[7].bias.data_ptr(), _gptr(a[7].weight), _gptr(a[7].bias)
+        self.cont = m.action_type in ("Continuous", "Continous")
+        p.cont = int(self.cont)
+        if m.action_type != "Discrete":
+            p.log_std, p.d_log_std = dec.log_std.data_ptr(), _gptr(dec.log_std)
+        else:
+            self.std = torch.ones(m.action_dim, device=a[7].weight.device)
+            p.log_std, p.d_log_std = self.std.data_ptr(), None
+        self.p, self.sig = p, s
+
+    def _n_disc(self, L):
+        m = self.model
+        if m.action_type == "Discrete":
+            return L
+        return 0 if self.cont else L + m.semi_index
+
+    def _geom(self, B, L, od, spread=False):
+        SQ, NRP, _ = geometry(L)
+        if spread:
+            SQ, NRP = _spread(B, L, SQ, NRP, self.model.decoder.mlp[1].weight.device)
+        p = self.p
+        p.Bs, p.L, p.od, p.A, p.SQ, p.NRP, p.n_disc = B, L, od, self.model.action_dim, SQ, NRP, self._n_disc(L)
+
+    def _obs(self, obs, idx):
+        if obs is None:
+            ectx = getattr(self.enc, "ctx", None)
+            if ectx is None:
+                raise RuntimeError("ActorFused.forward: no observations (pass obs=, or run the encoder forward first)")
+            obs, eidx = ectx[0], ectx[-1]
+            if (eidx is None) != (idx is None) or (idx is not None and eidx.data_ptr() != idx.data_ptr()):
+                raise RuntimeError("ActorFused.forward: the encoder's forward read other rows (idx differs)")
+        obs = obs.float().contiguous()
+        if obs.shape[-1] > MAX_FUSED_OBS:
+            raise RuntimeError(f"ActorFused: obs_dim {obs.shape[-1]} > {MAX_FUSED_OBS}")
+        return obs
+
+    def forward(self, rep, actions, ava=None, save=True, idx=None, obs=None):
+        """(logp, ent) of the stored actions.  ``rep`` gives the minibatch shape only; ``idx`` (int64 [B]): obs / actions /
+        ava are the rollout buffer's (N, L, .) rows, read through idx in-kernel."""
+        m = self.model
+        self._build()
+        B, L = rep.shape[:2]
+        dev = rep.device
+        n_tok = B * L
+        obs = self._obs(obs, idx)
+        A = m.action_dim
+        nact = nlp = A if self.cont else 1
+        nrow = B if idx is None else actions.shape[0]
+        if obs.shape[0] != nrow or obs.shape[1] != L:
+            raise ValueError(f"observations {tuple(obs.shape)}: expected ({nrow}, {L}, od)")
+        act = actions.reshape(nrow, L, nact).float().contiguous()
+        ava_c = ava.float().contiguous() if (ava is not None and not self.cont) else None
+        if ava_c is not None and ava_c.numel() != nrow * L * A:
+            raise ValueError(f"available actions {tuple(ava.shape)}: expected ({nrow}, {L}, {A})")
+        logp = torch.empty(B, L, nlp, device=dev)
+        ent = torch.empty(B, L, nlp, device=dev)
+        self._geom(B, L, obs.shape[-1])
+        p = self.p
+        p.obs, p.act, p.ava, p.logp, p.ent = obs.data_ptr(), act.data_ptr(), _ptr(ava_c), logp.data_ptr(), ent.data_ptr()
+        p.logits, p.dlogp, p.dent, p.sidx = None, None, None, _ptr(idx)
+        saves = []
+        if save:
+            sv = torch.empty(5, n_tok, 64, device=dev, dtype=torch.bfloat16)   # W_2 input; x-hat, GELU' of both stages
+            rs = torch.empty(2, n_tok, device=dev)
+            saves += [sv, rs]
+            p.sv_head = sv[0].data_ptr()
+            p.hs = HSv(sv[1].data_ptr(), sv[2].data_ptr(), rs[0].data_ptr())
+            p.es = HSv(sv[3].data_ptr(), sv[4].data_ptr(), rs[1].data_ptr())
+        else:
+            p.sv_head, p.hs, p.es = None, HSv(), HSv()
+        check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), int(save), kernels._stream()), "mat_actor_fwd")
+        self.ctx = (rep, act, ava_c, logp, ent, saves, obs, p.sv_head, HSv.from_buffer_copy(p.hs),
+                    HSv.from_buffer_copy(p.es), idx)
+        return logp, ent
+
+    @torch.no_grad()
+    def logits(self, obs):
+        """obs (B, L, od) -> the actor's logits (B, L, A) f32 (rollout: nothing saved, the batch spread over the CUs)."""
+        m = self.model
+        self._build()
+        obs = self._obs(obs, None)
+        B, L, od = obs.shape
+        out = torch.empty(B, L, m.action_dim, device=obs.device)
+        self._geom(B, L, od, spread=True)
+        p = self.p
+        p.obs, p.act, p.ava, p.logp, p.ent, p.logits = obs.data_ptr(), None, None, None, None, out.data_ptr()
+        p.dlogp, p.dent, p.sidx, p.sv_head, p.hs, p.es = None, None, None, None, HSv(), HSv()
+        p.g_delta, p.g_stride, p.g_copies, p.g_mode = 0, 0, 0, 0
+        try:
+            check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), 0, kernels._stream()), "mat_actor_fwd")
+        finally:
+            p.logits = None
+        return out
+
+    def backward(self, dlogp, dent):
+        m = self.model
+        rep, act, ava_c, logp, ent, saves, obs, head, hs, es, idx = self.ctx
+        if not saves:
+            raise RuntimeError("ActorFused.backward: the forward saved nothing (save=False)")
+        self._build()
+        B, L = rep.shape[:2]
+        self._geom(B, L, obs.shape[-1])
+        p = self.p
+        dlogp = dlogp.reshape(-1).float().contiguous()
+        dent = dent.reshape(-1).float().contiguous()
+        p.obs, p.act, p.ava, p.sidx = obs.data_ptr(), act.data_ptr(), _ptr(ava_c), _ptr(idx)
+        p.logp, p.ent, p.logits = logp.data_ptr(), ent.data_ptr(), None
+        p.dlogp, p.dent, p.sv_head, p.hs, p.es = dlogp.data_ptr(), dent.data_ptr(), head, hs, es
+        _set_workspace(p, m, B, p.SQ)
+        check(lib().mdl_mat_actor_bwd_ct(ctypes.byref(p), kernels._stream()), "mat_actor_bwd")
+        # the actor does not read rep: d rep is identically zero (one cached tensor per shape, never written)
+        z = self._zero
+        if z is None or z.shape != rep.shape or z.device != rep.device:
+            z = self._zero = torch.zeros(rep.shape, device=rep.device)
+        return z
+
+
 class _MATFusedFn(torch.autograd.Function):
     """(anchor, obs, actions, ava) -> (logp, values, entropy); backward runs the fused decoder then encoder
     backward kernels, which write the parameter gradients straight into ``.grad``."""
@@ -827,7 +1030,9 @@ def flat_range(params, flat):
 def _state(model, dev):
     st = getattr(model, "_mdl_train_state", None)
     if st is None:
-        st = (EncoderFused(model), DecoderFused(model), torch.zeros((), device=dev, requires_grad=True))
+        enc = EncoderFused(model)
+        dec = ActorFused(model, enc) if model.decoder.dec_actor else DecoderFused(model)
+        st = (enc, dec, torch.zeros((), device=dev, requires_grad=True))
         model._mdl_train_state = st
     return st
 

@@ -59,12 +59,14 @@ def kernel_report(runner) -> dict:
         out.update(encoder=_hip("", why), decode=_hip("", why), train=_hip("", why))
     else:
         out["encoder"] = _hip("mat_enc_fwd", reason or mat_train.encoder_unsupported_reasons(m))
-        out["decode"] = _hip("mat_decode", reason or mat_fused.unsupported_reasons(m))
-        if hasattr(m, "_mdl_decode_path") and out["decode"].startswith("hip:"):   # set by the last decode call
+        # MAT-Dec (dec_actor): the rollout is one pass of the fused actor forward, and it is the learner's decoder stage
+        actor = bool(getattr(getattr(m, "decoder", None), "dec_actor", False))
+        out["decode"] = _hip("mat_actor_fwd" if actor else "mat_decode", reason or mat_fused.unsupported_reasons(m))
+        if not actor and hasattr(m, "_mdl_decode_path") and out["decode"].startswith("hip:"):   # set by the last decode call
             out["decode"] += f"[{m._mdl_decode_path}]"
         tr = getattr(runner, "trainer", None)
         if tr is not None and getattr(tr, "fused", False):
-            out["train"] = "hip:mat_enc_fwd/bwd+mat_dec_fwd/bwd+ppo_loss+adam"
+            out["train"] = f"hip:mat_enc_fwd/bwd+{'mat_actor' if actor else 'mat_dec'}_fwd/bwd+ppo_loss+adam"
             if getattr(tr, "obs_embed_grad", None):   # wide observations: how the embedding backward sums
                 out["train"] += f"+obs_embed_fwd/bwd[grad={tr.obs_embed_grad}]"
         elif not reason and getattr(pol, "_enc_fused", lambda: False)() and mat_train.decoder_unsupported_reasons(m):
