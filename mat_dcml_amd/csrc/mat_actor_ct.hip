@@ -4,54 +4,33 @@
 //
 // The actor is two stages the training kernels already hold, run back to back on one token tile with no attention, no
 // cross attention and no LDS in the forward:
-//  * LN(od) -> Linear(od, 64) -> GELU -> LN: the encoder's observation embedding and its ln (mat_enc_ct.hip obs_ln /
-//    we_frags / embed_pre / ln_fwd_ct; backward: the embedding part of enc_bwd_tile);
+//  * LN(od) -> Linear(od, 64) -> GELU -> LN: the encoder's observation embedding and its ln (mat_embed_ct.h obs_ln /
+//    we_frags / embed_pre, always the in-kernel embedding: EncX{nullptr, nullptr}; the loops around them are those of
+//    enc_fwd_tile / enc_bwd_tile without the pre_in branches);
 //  * Linear(64, 64) -> GELU -> LN -> Linear(64, A) + the categorical / Normal statistics and masks: the decoder's
-//    action head (mat_dec_ct.hip head_fwd_ct / head_bwd_ct).
-// Both files are included for their device functions only (MDL_CT_NO_API); the kernel argument ActP is viewed as the
-// EncP / DecP fields those functions read (locals that never leave registers: the unused fields fold away).
+//    action head (mat_head_ct.h head_fwd_ct / head_bwd_ct).
+// Both headers take the kernel argument ActP as it is (they read the fields it shares by name with EncP / DecP).  This
+// file holds the actor's own tiles, kernels and host API.
 // The backward runs on the persistent grid of the other training backwards (launch_ct, chunk plan and stagger of
 // FOR_TILES), so a minibatch's backwards all write the same mdl_ct_bwd_grid(B, SQ) private gradient copies.
-#define MDL_CT_NO_API
-#include "mat_enc_ct.hip"
-#include "mat_dec_ct.hip"
+//
+// LayerNorm: the two-pass form (mat_train_ct.h ln_fwd_ct), for this unit and its backward wrapper
+// mat_actor_ct_bwd.hip, as in the encoder's units.  The decoder's units build the one-pass form, so the actor's action
+// head and the decoder's action head — the same head_fwd_ct source — sum their LayerNorm statistics in different
+// orders and differ in the last bits.  Each is pinned by its own tests (tests/test_gpu_dec_actor_train.py: fp64 parity,
+// bitwise repeats, rollout vs learner for the actor); changing this value changes the actor's bits.
+#define MDL_LN_ONEPASS 0
+#include "mat_train_ct.h"
+#include "mat_embed_ct.h"
+#include "mat_head_ct.h"
 
 namespace {
-
-__device__ __forceinline__ EncP actor_enc_view(const ActP& a) {
-  EncP p = {};
-  p.Bs = a.Bs; p.L = a.L; p.od = a.od; p.SQ = a.SQ; p.NRP = a.NRP; p.n_obj = 1;
-  p.obs = a.obs;
-  p.lno_g = a.lno_g; p.lno_b = a.lno_b; p.we = a.we; p.be = a.be; p.ln0_g = a.ln0_g; p.ln0_b = a.ln0_b;
-  p.d_lno_g = a.d_lno_g; p.d_lno_b = a.d_lno_b; p.d_we = a.d_we; p.d_be = a.d_be;
-  p.d_ln0_g = a.d_ln0_g; p.d_ln0_b = a.d_ln0_b;
-  p.es = a.es;
-  p.g_delta = a.g_delta; p.g_stride = a.g_stride; p.g_copies = a.g_copies; p.g_mode = a.g_mode;
-  p.sidx = a.sidx;
-  return p;
-}
-
-__device__ __forceinline__ DecP actor_dec_view(const ActP& a) {
-  DecP p = {};
-  p.Bs = a.Bs; p.L = a.L; p.A = a.A; p.SQ = a.SQ; p.NRP = a.NRP; p.n_disc = a.n_disc;
-  p.act = a.act; p.ava = a.ava;
-  p.h1 = a.h1; p.lnh = a.lnh;
-  p.wh2 = a.wh2; p.bh2 = a.bh2; p.d_wh2 = a.d_wh2; p.d_bh2 = a.d_bh2;
-  p.log_std = a.log_std; p.d_log_std = a.d_log_std;
-  p.logp = a.logp; p.ent = a.ent; p.dlogp = a.dlogp; p.dent = a.dent;
-  p.sv_head = a.sv_head; p.hs = a.hs;
-  p.g_delta = a.g_delta; p.g_stride = a.g_stride; p.g_copies = a.g_copies; p.g_mode = a.g_mode;
-  p.cont = a.cont;
-  p.sidx = a.sidx;
-  return p;
-}
 
 // ============================================================================================== forward
 // LOGITS (rollout, never with SAVE): the head's unmasked logits [tok][A] leave instead of log-prob / entropy — the
 // same embedding, W_2, LayerNorm and logit products as the learner's pass; masking and sampling stay with the caller
 template <bool SAVE, int MA, bool CONT, bool LOGITS>
-__device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, const DecP& pd, char* smem, int seq0,
-                                               int nseq) {
+__device__ __forceinline__ void actor_fwd_tile(const ActP& a, char* smem, int seq0, int nseq) {
   const Ctx c = make_ctx(a, smem, seq0, nseq);
   if (c.nseq <= 0) return;
   const int lane = c.lane, g = lane >> 4;
@@ -59,21 +38,21 @@ __device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, co
   CT xr[MAXRT];
   {
     bf16x8 W[4];
-    we_frags(pe, W, lane);
-    const CT gam = ld_vec(pe.ln0_g, lane), bet = ld_vec(pe.ln0_b, lane);
+    we_frags(a, W, lane);
+    const CT gam = ld_vec(a.ln0_g, lane), bet = ld_vec(a.ln0_b, lane);
 #pragma unroll
     for (int k = 0; k < MAXRT; ++k) {
       const int rt = c.wave + NW * k;
       if (rt < c.NT) {
         float oh[4], hat[4];
-        CT pre = embed_pre(pe, ex, rt, W, oh, hat, c), xh;
+        CT pre = embed_pre(a, ex, rt, W, oh, hat, c), xh;
         if (SAVE) {   // x-hat, GELU'(pre), rstd for the backward (which recomputes none of the embedding forward)
           CT gp;
           gelu_ct_both(pre, gp);
           const float rs = ln_fwd_ct(pre, xh, xr[k], gam, bet);
-          st_g(pe.es.xh, c.tok0, rt, c.NR, ct_pack(xh), lane);
-          st_g(pe.es.gp, c.tok0, rt, c.NR, ct_pack(gp), lane);
-          st_tokf(pe.es.rs, rt, rs, c);
+          st_g(a.es.xh, c.tok0, rt, c.NR, ct_pack(xh), lane);
+          st_g(a.es.gp, c.tok0, rt, c.NR, ct_pack(gp), lane);
+          st_tokf(a.es.rs, rt, rs, c);
         } else {
           gelu_ct(pre);
           ln_fwd_ct(pre, xh, xr[k], gam, bet);
@@ -82,14 +61,14 @@ __device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, co
     }
   }
   if (!LOGITS) {
-    head_fwd_ct<MA, CONT, false>(pd, xr, SAVE, c);
+    head_fwd_ct<MA, CONT, false>(a, xr, SAVE, c);
     return;
   }
   HeadW<MA> W;
-  head_w<MA>(pd, W, lane);
+  head_w<MA>(a, W, lane);
   AFr H;
-  loadA(H, pd.h1.fa, lane);
-  const CT bh = ld_vec(pd.h1.b, lane), gam = ld_vec(pd.lnh.g, lane), bet = ld_vec(pd.lnh.b, lane);
+  loadA(H, a.h1.fa, lane);
+  const CT bh = ld_vec(a.h1.b, lane), gam = ld_vec(a.lnh.g, lane), bet = ld_vec(a.lnh.b, lane);
 #pragma unroll
   for (int k = 0; k < MAXRT; ++k) {
     const int rt = c.wave + NW * k;
@@ -102,7 +81,7 @@ __device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, co
       gelu_ct(hh);
       ln_fwd_ct(hh, xh, n, gam, bet);
       f32x4 L[MA];
-      head_logits_ct<MA>(pd, W, n, L, lane);
+      head_logits_ct<MA>(a, W, n, L, lane);
 #pragma unroll
       for (int ma = 0; ma < MA; ++ma)
 #pragma unroll
@@ -118,9 +97,7 @@ __device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncP& pe, co
 template <bool SAVE, int MA, bool CONT, bool LOGITS>
 __global__ __launch_bounds__(NTHR, FWD_WGPC) void mat_actor_fwd_ct(ActP a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const EncP pe = actor_enc_view(a);
-  const DecP pd = actor_dec_view(a);
-  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS>(a, pe, pd, smem, s0, ns)));
+  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS>(a, smem, s0, ns)));
 }
 #endif  // !MDL_CT_BWD_TU
 
@@ -133,8 +110,7 @@ __device__ __forceinline__ int actor_small_wg_slot0(const ActP& a) {
 }
 
 template <int MA, bool CONT>
-__device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, const DecP& pd, char* smem, int seq0,
-                                               int nseq, bool first) {
+__device__ __forceinline__ void actor_bwd_tile(const ActP& a, char* smem, int seq0, int nseq, bool first) {
   const Ctx c = make_ctx(a, smem, seq0, nseq, first);
   if (c.nseq <= 0) return;
   zero_pad_rows(c);
@@ -142,7 +118,7 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, con
   const int lane = c.lane;
   CT dx[MAXRT];
   // ---------------- head backward: dx = d LN0 output; d W_2, d W_h2, their biases, the head LayerNorm, log_std
-  head_bwd_ct<MA, CONT, false>(pd, dx, c, actor_small_wg_slot0(a));
+  head_bwd_ct<MA, CONT, false>(a, dx, c, actor_small_wg_slot0(a));
   // ---------------- embedding backward: x0 = LN0(GELU(pre)), pre = W_1 · LN_obs(obs) + b_1  (enc_bwd_tile)
   {
     CT dlg, dlb, dbe;
@@ -151,19 +127,19 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, con
     ct_zero(dbe);
     f32x4 dog = {0.f, 0.f, 0.f, 0.f}, dob = {0.f, 0.f, 0.f, 0.f};
     bf16x8 WT[2];
-    weT_frags(p, WT, lane);
-    const CT gam = ld_vec(p.ln0_g, lane);
+    weT_frags(a, WT, lane);
+    const CT gam = ld_vec(a.ln0_g, lane);
 #pragma unroll
     for (int k = 0; k < MAXRT; ++k) {
       const int rt = c.wave + NW * k;
       if (rt < c.NT) {
         const bool ok = tok_ok(rt, c);
         float oh[4] = {0.f, 0.f, 0.f, 0.f}, hat[4] = {0.f, 0.f, 0.f, 0.f};
-        obs_ln(p, rt, c, oh, hat);   // X of W_1 and the LN_obs backward (od <= 16 dims in-lane)
+        obs_ln(a, rt, c, oh, hat);   // X of W_1 and the LN_obs backward (od <= 16 dims in-lane)
         // the forward's x-hat, GELU'(pre) and rstd (no embedding product, GELU or LayerNorm forward here)
-        const CT xh = ct_unpack(ld_g(p.es.xh, c.tok0, rt, c.NR, lane)), egp = ct_unpack(ld_g(p.es.gp, c.tok0, rt, c.NR, lane));
+        const CT xh = ct_unpack(ld_g(a.es.xh, c.tok0, rt, c.NR, lane)), egp = ct_unpack(ld_g(a.es.gp, c.tok0, rt, c.NR, lane));
         CT de;
-        ln_bwd_ct(dx[k], xh, ld_tokf(p.es.rs, rt, c), gam, ok, de, dlg, dlb);
+        ln_bwd_ct(dx[k], xh, ld_tokf(a.es.rs, rt, c), gam, ok, de, dlg, dlb);
 #pragma unroll
         for (int i = 0; i < 4; ++i) de.v[i] *= egp.v[i];   // padded rows: zero
 #pragma unroll
@@ -188,9 +164,9 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, con
         }
       }
     }
-    flush_vec(dlg, c.g(p.d_ln0_g), 5, c);
-    flush_vec(dlb, c.g(p.d_ln0_b), 6, c);
-    flush_vec(dbe, c.g(p.d_be), 7, c);
+    flush_vec(dlg, c.g(a.d_ln0_g), 5, c);
+    flush_vec(dlb, c.g(a.d_ln0_b), 6, c);
+    flush_vec(dbe, c.g(a.d_be), 7, c);
     const int c16 = lane & 15, g = lane >> 4;
     float og = 0.f, ob = 0.f;
 #pragma unroll
@@ -200,12 +176,12 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, con
       ob = c16 == r ? s1 : ob;
     }
     const int dim = 4 * g + c16;
-    if (c16 < 4 && dim < p.od) {
-      if (p.d_lno_g) vacc_add(c.g(p.d_lno_g), 8, dim, og, c, p.od);
-      if (p.d_lno_b) vacc_add(c.g(p.d_lno_b), 9, dim, ob, c, p.od);
+    if (c16 < 4 && dim < a.od) {
+      if (a.d_lno_g) vacc_add(c.g(a.d_lno_g), 8, dim, og, c, a.od);
+      if (a.d_lno_b) vacc_add(c.g(a.d_lno_b), 9, dim, ob, c, a.od);
     }
     __syncthreads();
-    wgrad_g(c.DA, c.XB, c.KP, c.g(p.d_we), p.od, 64, p.od, nullptr, c.wave, lane, c.gm);
+    wgrad_g(c.DA, c.XB, c.KP, c.g(a.d_we), a.od, 64, a.od, nullptr, c.wave, lane, c.gm);
   }
 }
 
@@ -213,10 +189,8 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncP& p, con
 template <int MA, bool CONT>
 __global__ __launch_bounds__(NTHR, WGPC) void mat_actor_bwd_ct(ActP a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const EncP pe = actor_enc_view(a);
-  const DecP pd = actor_dec_view(a);
   vacc_begin(a, smem);
-  FOR_TILES(a, (actor_bwd_tile<MA, CONT>(a, pe, pd, smem, s0, ns, it_ == 0)));
+  FOR_TILES(a, (actor_bwd_tile<MA, CONT>(a, smem, s0, ns, it_ == 0)));
   vacc_end(a, smem);
 }
 #endif  // MDL_CT_BWD_TU

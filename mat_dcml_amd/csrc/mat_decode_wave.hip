@@ -23,7 +23,7 @@
 // self-attention q / K / V come from the per-token table (they depend only on the previous action), the
 // cross-attention queries W_q2 rep_i are precomputed before the agent loop, the head LayerNorm is folded into the
 // logit product (DecParams.hfold), sampling noise comes from in-kernel Philox (same streams as mat_decode.hip).
-#define MDL_LN_ONEPASS
+#define MDL_LN_ONEPASS 1   // the one-pass LayerNorm forward of mat_train_ct.h, as the decoder's training units
 #include "mat_train_ct.h"
 #include "decode_params.h"
 

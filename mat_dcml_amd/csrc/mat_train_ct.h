@@ -314,7 +314,13 @@ __device__ __forceinline__ float tok_sum(const CT& x) {
   for (int i = 0; i < 4; ++i) s += (x.v[i][0] + x.v[i][1]) + (x.v[i][2] + x.v[i][3]);
   return cross_row_sum(s);
 }
-#ifdef MDL_LN_ONEPASS   // the decoder translation units (measured: dec bwd -45 us, enc bwd +60 us with it)
+// Every translation unit picks its LayerNorm forward before including this header: MDL_LN_ONEPASS 1 (the decoder
+// units and the one-wave decode) or 0 (the encoder and MAT-Dec actor units).  The two forms sum in different orders, so
+// the choice fixes the unit's bits — it is set where the unit starts, never by include order.
+#ifndef MDL_LN_ONEPASS
+#error "define MDL_LN_ONEPASS to 0 (two-pass LayerNorm forward) or 1 (one-pass) before including mat_train_ct.h"
+#endif
+#if MDL_LN_ONEPASS   // the decoder translation units (measured: dec bwd -45 us, enc bwd +60 us with it)
 // y = LN(x) * gamma + beta; returns rstd, xh = normalised x.  One pass: Σx and Σx² of the token reduce side by side
 // (one cross-row exchange chain instead of two dependent ones), elementwise work on packed fp32 pairs.
 __device__ __forceinline__ float ln_fwd_ct(const CT& x, CT& xh, CT& y, const CT& gam, const CT& bet) {

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -95,6 +96,7 @@ sig("mdl_grad_reduce", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP
 sig("mdl_grad_reduce_norm", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP, VP)
 sig("mdl_grad_reduce_priv", VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, VP, VP)
 sig("mdl_ct_bwd_grid", ctypes.c_int, ctypes.c_int)
+sig("mdl_pack_weights", VP, ctypes.c_int, VP)
 
 
 class OEArgs(ctypes.Structure):   # csrc/obs_embed.hip
@@ -175,7 +177,7 @@ class ObsEmbed:
             self.up = torch.empty(OEB_UBLK * 128, device=dev)
         a = self._args(obs2d.shape[0], obs2d, None, stat, dpre)
         check(lib().mdl_obs_embed_bwd(ctypes.byref(a), kernels._stream()), "obs_embed_bwd")
-sig("mdl_pack_weights", VP, ctypes.c_int, VP)
+
 
 MAX_ACTION_DIM = 64
 
@@ -191,18 +193,10 @@ def _spread(B, L, SQ, NRP, dev):
 
 
 def geometry(L):
-    """(SQ sequences per tile, NRP padded rows, kernel suffix) of the training tiling for sequence length L
-    ((0, 0, "") when L does not fit)."""
+    """(SQ sequences per tile, NRP padded rows) of the training tiling for sequence length L ((0, 0) when L does not
+    fit)."""
     v = lib().mdl_mat_train_geometry_ct(L)
-    return (v & 0xFFFF, v >> 16, "_ct") if v else (0, 0, "")
-
-
-def _enc_fwd(sfx, p, pre_in, nb, save):
-    return lib().mdl_mat_enc_fwd_ct(ctypes.byref(p), pre_in, nb, int(save), kernels._stream())
-
-
-def _enc_bwd(sfx, p, pre_in, dpre_out, nb):
-    return lib().mdl_mat_enc_bwd_ct(ctypes.byref(p), pre_in, dpre_out, nb, kernels._stream())
+    return (v & 0xFFFF, v >> 16) if v else (0, 0)
 
 
 def _ptr(t):
@@ -281,6 +275,38 @@ def _ln(ln):
     return LNp(ln.weight.data_ptr(), ln.bias.data_ptr(), _gptr(ln.weight), _gptr(ln.bias))
 
 
+def _set_embed(p, ln_obs, lin, ln0):
+    """LN(od) -> Linear(od, 64) -> GELU -> LN: the six embedding fields of an EncP / ActP and their gradients."""
+    for name, t in (("lno_g", ln_obs.weight), ("lno_b", ln_obs.bias), ("we", lin.weight), ("be", lin.bias),
+                    ("ln0_g", ln0.weight), ("ln0_b", ln0.bias)):
+        setattr(p, name, t.data_ptr())
+        setattr(p, "d_" + name, _gptr(t))
+
+
+def _set_head(p, mp, lin1, ln, lin2, model):
+    """Linear(64, 64) -> GELU -> LN -> Linear(64, A): the action-head fields of a DecP / ActP and their gradients.
+    Returns the all-ones tensor log_std points at for a Discrete head (no log_std parameter: no gradient), else None;
+    the caller keeps it alive."""
+    p.h1 = mp.mat(lin1)
+    p.lnh = _ln(ln)
+    p.wh2, p.bh2, p.d_wh2, p.d_bh2 = lin2.weight.data_ptr(), lin2.bias.data_ptr(), _gptr(lin2.weight), _gptr(lin2.bias)
+    if model.action_type != "Discrete":
+        p.log_std, p.d_log_std = model.decoder.log_std.data_ptr(), _gptr(model.decoder.log_std)
+        return None
+    ones = torch.ones(model.action_dim, device=lin2.weight.device)
+    p.log_std, p.d_log_std = ones.data_ptr(), None
+    return ones
+
+
+def _n_disc(model, L):
+    """Leading agents of a sequence with a categorical head (Semi_Discrete: all but the last -semi_index)."""
+    if model.action_type == "Discrete":
+        return L
+    if model.action_type in ("Continuous", "Continous") or model.action_type in AVAIL_CONT_TYPES:
+        return 0
+    return L + model.semi_index
+
+
 def _grad_sig(model):
     """Gradient-pointer signature the packed kernel arguments were built against: the first encoder AND decoder
     parameter (the hybrid path creates encoder gradients separately from the decoder's autograd ones)."""
@@ -312,7 +338,7 @@ def encoder_unsupported_reasons(model):
 
 AVAIL_CONT_TYPES = ("Available_Continuous", "Available_Continous")
 AVAIL_CONT_ENV = "MAT_DCML_AVAIL_CONT_TRAIN"
-AVAIL_CONT_MIN_A, AVAIL_CONT_MAX_A = 3, 16   # one logit tile of the action head (csrc/mat_dec_ct.hip)
+AVAIL_CONT_MIN_A, AVAIL_CONT_MAX_A = 3, 16   # one logit tile of the action head (csrc/mat_head_ct.h)
 
 
 def avail_cont_train_mode():
@@ -399,6 +425,49 @@ def supported(model):
     return encoder_supported(model) and decoder_supported(model)
 
 
+# ------------------------------------------------------------------------------------------------- forward records
+# What a forward leaves in ``.ctx`` for its backward (None: nothing pending).  ``saves`` keeps the saved-activation
+# tensors alive; ``svs`` / ``hs`` / ``es`` are copies of the pointer structs the forward launched with.
+class EncCtx(NamedTuple):
+    obs: torch.Tensor
+    rep: torch.Tensor
+    v: torch.Tensor
+    saves: list
+    svs: list
+    pre: Optional[torch.Tensor]    # wide observations: the embedding pre-activation and its LayerNorm statistics
+    stat: Optional[torch.Tensor]
+    hs: HSv
+    es: HSv
+    idx: Optional[torch.Tensor]
+
+
+class DecCtx(NamedTuple):
+    rep: torch.Tensor
+    act: torch.Tensor
+    ava: Optional[torch.Tensor]
+    logp: torch.Tensor
+    ent: torch.Tensor
+    saves: list
+    svs: list
+    head: Optional[int]            # sv_head pointer
+    hs: HSv
+    idx: Optional[torch.Tensor]
+
+
+class ActCtx(NamedTuple):
+    rep: torch.Tensor
+    act: torch.Tensor
+    ava: Optional[torch.Tensor]
+    logp: torch.Tensor
+    ent: torch.Tensor
+    saves: list
+    obs: torch.Tensor
+    head: Optional[int]            # sv_head pointer
+    hs: HSv
+    es: HSv
+    idx: Optional[torch.Tensor]
+
+
 # ------------------------------------------------------------------------------------------------- encoder
 class EncoderFused:
     def __init__(self, model):
@@ -414,11 +483,7 @@ class EncoderFused:
         mp = model_pack(m)
         enc = m.encoder
         p = EncP()
-        ln_o, lin_e = enc.obs_encoder[0], enc.obs_encoder[1]
-        for name, t in (("lno_g", ln_o.weight), ("lno_b", ln_o.bias), ("we", lin_e.weight), ("be", lin_e.bias),
-                        ("ln0_g", enc.ln.weight), ("ln0_b", enc.ln.bias)):
-            setattr(p, name, t.data_ptr())
-            setattr(p, "d_" + name, _gptr(t))
+        _set_embed(p, enc.obs_encoder[0], enc.obs_encoder[1], enc.ln)
         for bi, blk in enumerate(enc.blocks):
             a = blk.attn
             for slot, lin in ((0, a.query), (1, a.key), (2, a.value), (3, a.proj), (8, blk.mlp[0]), (9, blk.mlp[2])):
@@ -448,7 +513,7 @@ class EncoderFused:
         _, L, od = obs.shape
         B = obs.shape[0] if idx is None else idx.numel()
         dev = obs.device
-        SQ, NRP, sfx = geometry(L)
+        SQ, NRP = geometry(L)
         if not save:   # rollout / value passes: small batches — spread them over every CU (nothing is saved, so
             SQ, NRP = _spread(B, L, SQ, NRP, dev)   # the backward's tiling need not match)
         n_tok = B * L
@@ -473,9 +538,9 @@ class EncoderFused:
                 lse = torch.empty(n_tok, 2, device=dev)
                 rs = torch.empty(3, n_tok, device=dev)   # LayerNorm rstd, slot-major
                 saves += [t, lse, rs]
-                p.sv[bi] = Sv(t[0].data_ptr(), t[1].data_ptr(), lse.data_ptr(), t[2].data_ptr(), None, None, None,
-                              t[3].data_ptr(), t[4].data_ptr(), None, t[5].data_ptr(), t[6].data_ptr(), t[7].data_ptr(),
-                              None, rs.data_ptr())
+                p.sv[bi] = Sv(xin=t[0].data_ptr(), a1=t[1].data_ptr(), lse1=lse.data_ptr(), x1=t[2].data_ptr(),
+                              g=t[3].data_ptr(), a1lo=t[4].data_ptr(), gp=t[5].data_ptr(), xh0=t[6].data_ptr(),
+                              xh1=t[7].data_ptr(), rs=rs.data_ptr())
             hv = torch.empty(4, n_tok, 64, device=dev, dtype=torch.bfloat16)   # head / embedding x-hat, GELU'
             hr = torch.empty(2, n_tok, device=dev)                              # head / embedding rstd
             saves += [hv, hr]
@@ -483,25 +548,26 @@ class EncoderFused:
             p.es = HSv(hv[2].data_ptr(), hv[3].data_ptr(), hr[1].data_ptr())
         else:
             p.hs, p.es = HSv(), HSv()
-        check(_enc_fwd(sfx, p, _ptr(pre), m.n_block, save), "mat_enc_fwd")
-        self.ctx = (obs, rep, v, saves, [Sv.from_buffer_copy(p.sv[i]) for i in range(m.n_block)], pre, stat,
-                    HSv.from_buffer_copy(p.hs), HSv.from_buffer_copy(p.es), idx)
+        check(lib().mdl_mat_enc_fwd_ct(ctypes.byref(p), _ptr(pre), m.n_block, int(save), kernels._stream()), "mat_enc_fwd")
+        self.ctx = EncCtx(obs=obs, rep=rep, v=v, saves=saves, svs=[Sv.from_buffer_copy(p.sv[i]) for i in range(m.n_block)],
+                          pre=pre, stat=stat, hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx)
         return v, rep
 
     def backward(self, drep, dv):
         m = self.model
-        obs, rep, v, saves, svs, pre, stat, hs, es, idx = self.ctx
+        x = self.ctx
+        obs, rep, v, pre = x.obs, x.rep, x.v, x.pre
         self._build()
         p = self.p
-        p.hs, p.es = hs, es
+        p.hs, p.es = x.hs, x.es
         drep = drep.float().contiguous()
         dv = dv.float().contiguous()
         B, L, od = rep.shape[0], obs.shape[1], obs.shape[2]
-        SQ, NRP, sfx = geometry(L)
+        SQ, NRP = geometry(L)
         p.Bs, p.L, p.od, p.SQ, p.NRP, p.n_obj = B, L, od, SQ, NRP, m.n_objective
         p.obs, p.rep, p.v, p.drep, p.dv = obs.data_ptr(), rep.data_ptr(), v.data_ptr(), drep.data_ptr(), dv.data_ptr()
-        p.sidx = _ptr(idx)
-        for i, s in enumerate(svs):
+        p.sidx = _ptr(x.idx)
+        for i, s in enumerate(x.svs):
             p.sv[i] = s
         _set_workspace(p, m, B, SQ)
         dpre = torch.empty_like(pre) if pre is not None else None
@@ -510,9 +576,9 @@ class EncoderFused:
         p.d_bh2 = b.grad.data_ptr() if in_kernel else None
         if in_kernel and p.g_copies:
             check_grad_ptrs(p, m._mdl_gws_buf[1])
-        check(_enc_bwd(sfx, p, _ptr(pre), _ptr(dpre), m.n_block), "mat_enc_bwd")
+        check(lib().mdl_mat_enc_bwd_ct(ctypes.byref(p), _ptr(pre), _ptr(dpre), m.n_block, kernels._stream()), "mat_enc_bwd")
         if pre is not None:
-            self.emb.backward(obs.view(-1, od), stat, dpre)
+            self.emb.backward(obs.view(-1, od), x.stat, dpre)
         if b.grad is not None and not in_kernel:
             b.grad.add_(dv.reshape(-1, dv.shape[-1]).sum(0))
 
@@ -549,31 +615,15 @@ class DecoderFused:
             p.blk[bi].ln[0] = _ln(blk.ln1)
             p.blk[bi].ln[1] = _ln(blk.ln2)
             p.blk[bi].ln[2] = _ln(blk.ln3)
-        p.h1 = mp.mat(dec.head[0])
-        p.lnh = _ln(dec.head[2])
-        h3 = dec.head[3]
-        p.wh2, p.bh2, p.d_wh2, p.d_bh2 = h3.weight.data_ptr(), h3.bias.data_ptr(), _gptr(h3.weight), _gptr(h3.bias)
-        if m.action_type != "Discrete":
-            self.std = torch.empty(m.action_dim, device=h3.weight.device)
-            p.log_std, p.stdv, p.d_log_std = dec.log_std.data_ptr(), self.std.data_ptr(), _gptr(dec.log_std)
-        else:
-            self.std = torch.ones(m.action_dim, device=h3.weight.device)
-            p.log_std, p.stdv, p.d_log_std = self.std.data_ptr(), self.std.data_ptr(), None
+        ones = _set_head(p, mp, dec.head[0], dec.head[2], dec.head[3], m)
+        self.std = ones if ones is not None else torch.empty(m.action_dim, device=dec.head[3].weight.device)
+        p.stdv = self.std.data_ptr()
         self.p, self.sig = p, s
 
-    def _n_disc(self, L):
-        m = self.model
-        if m.action_type == "Discrete":
-            return L
-        if m.action_type in ("Continuous", "Continous") or m.action_type in AVAIL_CONT_TYPES:
-            return 0
-        return L + m.semi_index
-
     def _geom(self, B, L):
-        SQ, NRP, sfx = geometry(L)
+        SQ, NRP = geometry(L)
         p = self.p
-        p.Bs, p.L, p.A, p.SQ, p.NRP, p.n_disc = B, L, self.model.action_dim, SQ, NRP, self._n_disc(L)
-        return sfx
+        p.Bs, p.L, p.A, p.SQ, p.NRP, p.n_disc = B, L, self.model.action_dim, SQ, NRP, _n_disc(self.model, L)
 
     def forward(self, rep, actions, ava=None, save=True, idx=None):
         """``idx`` (int64 [B]): actions / ava are the rollout buffer's (N, L, .) rows, read through idx in-kernel."""
@@ -596,7 +646,7 @@ class DecoderFused:
             raise ValueError(f"available actions {tuple(ava.shape)}: expected ({nrow}, {L}, {A})")
         logp = torch.empty(B, L, nlp, device=dev)
         ent = torch.empty(B, L, nlp, device=dev)
-        sfx = self._geom(B, L)
+        self._geom(B, L)
         p = self.p
         p.act, p.ava, p.rep, p.logp, p.ent = act.data_ptr(), _ptr(ava_c), rep.data_ptr(), logp.data_ptr(), ent.data_ptr()
         p.sidx = _ptr(idx)
@@ -607,9 +657,10 @@ class DecoderFused:
                 lse = torch.empty(2, n_tok, 2, device=dev)
                 rs = torch.empty(3, n_tok, device=dev)   # LayerNorm rstd, slot-major
                 saves += [t, lse, rs]
-                p.sv[bi] = Sv(t[0].data_ptr(), t[1].data_ptr(), lse[0].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                              lse[1].data_ptr(), t[4].data_ptr(), t[5].data_ptr(), t[6].data_ptr(), t[7].data_ptr(),
-                              t[8].data_ptr(), t[9].data_ptr(), t[10].data_ptr(), t[11].data_ptr(), rs.data_ptr())
+                p.sv[bi] = Sv(xin=t[0].data_ptr(), a1=t[1].data_ptr(), lse1=lse[0].data_ptr(), x1=t[2].data_ptr(),
+                              a2=t[3].data_ptr(), lse2=lse[1].data_ptr(), x2=t[4].data_ptr(), g=t[5].data_ptr(),
+                              a1lo=t[6].data_ptr(), a2lo=t[7].data_ptr(), gp=t[8].data_ptr(), xh0=t[9].data_ptr(),
+                              xh1=t[10].data_ptr(), xh2=t[11].data_ptr(), rs=rs.data_ptr())
             head = torch.empty(3, n_tok, 64, device=dev, dtype=torch.bfloat16)   # head input, x-hat, GELU'
             hr = torch.empty(n_tok, device=dev)
             saves += [head, hr]
@@ -617,29 +668,31 @@ class DecoderFused:
             p.hs = HSv(head[1].data_ptr(), head[2].data_ptr(), hr.data_ptr())
         else:
             p.hs = HSv()
-        check(getattr(lib(), "mdl_mat_dec_fwd" + sfx)(ctypes.byref(p), m.n_block, int(save), kernels._stream()), "mat_dec_fwd")
-        self.ctx = (rep, act, ava_c, logp, ent, saves, [Sv.from_buffer_copy(p.sv[i]) for i in range(m.n_block)],
-                    p.sv_head, HSv.from_buffer_copy(p.hs), idx)
+        check(lib().mdl_mat_dec_fwd_ct(ctypes.byref(p), m.n_block, int(save), kernels._stream()), "mat_dec_fwd")
+        self.ctx = DecCtx(rep=rep, act=act, ava=ava_c, logp=logp, ent=ent, saves=saves,
+                          svs=[Sv.from_buffer_copy(p.sv[i]) for i in range(m.n_block)], head=p.sv_head,
+                          hs=HSv.from_buffer_copy(p.hs), idx=idx)
         return logp, ent
 
     def backward(self, dlogp, dent):
         m = self.model
-        rep, act, ava_c, logp, ent, saves, svs, head, hs, idx = self.ctx
+        x = self.ctx
+        rep = x.rep
         self._build()
         B, L = rep.shape[:2]
-        sfx = self._geom(B, L)
+        self._geom(B, L)
         p = self.p
         dlogp = dlogp.reshape(-1).float().contiguous()
         dent = dent.reshape(-1).float().contiguous()
         # the backward writes every row of d rep (its last decoder block overwrites)
         drep = torch.empty_like(rep)
-        p.act, p.ava, p.rep, p.sidx = act.data_ptr(), _ptr(ava_c), rep.data_ptr(), _ptr(idx)
-        p.dlogp, p.dent, p.drep, p.sv_head = dlogp.data_ptr(), dent.data_ptr(), drep.data_ptr(), head
-        p.hs = hs
-        for i, s in enumerate(svs):
+        p.act, p.ava, p.rep, p.sidx = x.act.data_ptr(), _ptr(x.ava), rep.data_ptr(), _ptr(x.idx)
+        p.dlogp, p.dent, p.drep, p.sv_head = dlogp.data_ptr(), dent.data_ptr(), drep.data_ptr(), x.head
+        p.hs = x.hs
+        for i, s in enumerate(x.svs):
             p.sv[i] = s
         _set_workspace(p, m, B, p.SQ)
-        check(getattr(lib(), "mdl_mat_dec_bwd" + sfx)(ctypes.byref(p), m.n_block, kernels._stream()), "mat_dec_bwd")
+        check(lib().mdl_mat_dec_bwd_ct(ctypes.byref(p), m.n_block, kernels._stream()), "mat_dec_bwd")
         return drep
 
 
@@ -669,41 +722,25 @@ class ActorFused:
         mp = model_pack(m)
         a = dec.mlp
         p = ActP()
-        for name, t in (("lno_g", a[0].weight), ("lno_b", a[0].bias), ("we", a[1].weight), ("be", a[1].bias),
-                        ("ln0_g", a[3].weight), ("ln0_b", a[3].bias)):
-            setattr(p, name, t.data_ptr())
-            setattr(p, "d_" + name, _gptr(t))
-        p.h1 = mp.mat(a[4])
-        p.lnh = _ln(a[6])
-        p.wh2, p.bh2, p.d_wh2, p.d_bh2 = a[7].weight.data_ptr(), a[7].bias.data_ptr(), _gptr(a[7].weight), _gptr(a[7].bias)
+        _set_embed(p, a[0], a[1], a[3])
+        self.std = _set_head(p, mp, a[4], a[6], a[7], m)
         self.cont = m.action_type in ("Continuous", "Continous")
         p.cont = int(self.cont)
-        if m.action_type != "Discrete":
-            p.log_std, p.d_log_std = dec.log_std.data_ptr(), _gptr(dec.log_std)
-        else:
-            self.std = torch.ones(m.action_dim, device=a[7].weight.device)
-            p.log_std, p.d_log_std = self.std.data_ptr(), None
         self.p, self.sig = p, s
 
-    def _n_disc(self, L):
-        m = self.model
-        if m.action_type == "Discrete":
-            return L
-        return 0 if self.cont else L + m.semi_index
-
     def _geom(self, B, L, od, spread=False):
-        SQ, NRP, _ = geometry(L)
+        SQ, NRP = geometry(L)
         if spread:
             SQ, NRP = _spread(B, L, SQ, NRP, self.model.decoder.mlp[1].weight.device)
         p = self.p
-        p.Bs, p.L, p.od, p.A, p.SQ, p.NRP, p.n_disc = B, L, od, self.model.action_dim, SQ, NRP, self._n_disc(L)
+        p.Bs, p.L, p.od, p.A, p.SQ, p.NRP, p.n_disc = B, L, od, self.model.action_dim, SQ, NRP, _n_disc(self.model, L)
 
     def _obs(self, obs, idx):
         if obs is None:
             ectx = getattr(self.enc, "ctx", None)
             if ectx is None:
                 raise RuntimeError("ActorFused.forward: no observations (pass obs=, or run the encoder forward first)")
-            obs, eidx = ectx[0], ectx[-1]
+            obs, eidx = ectx.obs, ectx.idx
             if (eidx is None) != (idx is None) or (idx is not None and eidx.data_ptr() != idx.data_ptr()):
                 raise RuntimeError("ActorFused.forward: the encoder's forward read other rows (idx differs)")
         obs = obs.float().contiguous()
@@ -746,8 +783,8 @@ class ActorFused:
         else:
             p.sv_head, p.hs, p.es = None, HSv(), HSv()
         check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), int(save), kernels._stream()), "mat_actor_fwd")
-        self.ctx = (rep, act, ava_c, logp, ent, saves, obs, p.sv_head, HSv.from_buffer_copy(p.hs),
-                    HSv.from_buffer_copy(p.es), idx)
+        self.ctx = ActCtx(rep=rep, act=act, ava=ava_c, logp=logp, ent=ent, saves=saves, obs=obs, head=p.sv_head,
+                          hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx)
         return logp, ent
 
     @torch.no_grad()
@@ -771,8 +808,9 @@ class ActorFused:
 
     def backward(self, dlogp, dent):
         m = self.model
-        rep, act, ava_c, logp, ent, saves, obs, head, hs, es, idx = self.ctx
-        if not saves:
+        x = self.ctx
+        rep, obs = x.rep, x.obs
+        if not x.saves:
             raise RuntimeError("ActorFused.backward: the forward saved nothing (save=False)")
         self._build()
         B, L = rep.shape[:2]
@@ -780,9 +818,9 @@ class ActorFused:
         p = self.p
         dlogp = dlogp.reshape(-1).float().contiguous()
         dent = dent.reshape(-1).float().contiguous()
-        p.obs, p.act, p.ava, p.sidx = obs.data_ptr(), act.data_ptr(), _ptr(ava_c), _ptr(idx)
-        p.logp, p.ent, p.logits = logp.data_ptr(), ent.data_ptr(), None
-        p.dlogp, p.dent, p.sv_head, p.hs, p.es = dlogp.data_ptr(), dent.data_ptr(), head, hs, es
+        p.obs, p.act, p.ava, p.sidx = obs.data_ptr(), x.act.data_ptr(), _ptr(x.ava), _ptr(x.idx)
+        p.logp, p.ent, p.logits = x.logp.data_ptr(), x.ent.data_ptr(), None
+        p.dlogp, p.dent, p.sv_head, p.hs, p.es = dlogp.data_ptr(), dent.data_ptr(), x.head, x.hs, x.es
         _set_workspace(p, m, B, p.SQ)
         check(lib().mdl_mat_actor_bwd_ct(ctypes.byref(p), kernels._stream()), "mat_actor_bwd")
         # the actor does not read rep: d rep is identically zero (one cached tensor per shape, never written)
@@ -810,10 +848,10 @@ class _MATFusedFn(torch.autograd.Function):
         dec, enc = ctx.dec, ctx.enc
         enc.ctx, dec.ctx = ctx.saved
         ctx.saved = None
-        logp, ent = dec.ctx[3], dec.ctx[4]
+        logp, ent = dec.ctx.logp, dec.ctx.ent
         drep = dec.backward(dlogp if dlogp is not None else torch.zeros_like(logp),
                             dent if dent is not None else torch.zeros_like(ent))
-        enc.backward(drep, dv if dv is not None else torch.zeros_like(enc.ctx[2]))
+        enc.backward(drep, dv if dv is not None else torch.zeros_like(enc.ctx.v))
         dec.ctx = None
         enc.ctx = None
         return torch.zeros((), device=drep.device), None, None, None, None, None
@@ -1064,7 +1102,7 @@ class _EncFusedFn(torch.autograd.Function):
     def backward(ctx, dv, drep):
         enc = ctx.enc
         enc.ctx, ctx.saved = ctx.saved, None
-        v, rep = enc.ctx[2], enc.ctx[1]
+        v, rep = enc.ctx.v, enc.ctx.rep
         enc.backward(drep if drep is not None else torch.zeros_like(rep),
                      dv if dv is not None else torch.zeros_like(v))
         enc.ctx = None

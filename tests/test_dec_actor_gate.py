@@ -119,23 +119,40 @@ def test_shared_actor_matrix_is_packed():
     assert mat_train.decoder_linears(_mat(share_actor=False)) == []
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-def test_actor_arg_struct_matches_ctypes(tmp_path):
-    """ActP's ctypes mirror against the C struct's size and EVERY field offset, the C side compiled for the host from
-    the library's own header (the method of tests/test_build_guard.py)."""
+ARG_STRUCTS = ("EncP", "DecP", "ActP")
+PART_STRUCTS = ("Mat", "LNp", "Blk", "Sv", "HSv")
+
+
+@pytest.fixture(scope="module")
+def c_struct_layout(tmp_path_factory):
+    """{"sizeof X": bytes, "X.field": offset} of the kernel argument structs as the C compiler lays them out: one host
+    program compiled from the library's own header (the method of tests/test_build_guard.py), shared by the cases."""
     from mat_dcml_amd.ops import mat_train
     csrc = os.path.join(ROOT, "mat_dcml_amd", "csrc")
-    names = [n for n, _ in mat_train.ActP._fields_]
-    lines = "\n".join(f'  printf("{n} %zu\\n", offsetof(ActP, {n}));' for n in names)
-    src = tmp_path / "sz.hip"
+    lines = [f'  printf("sizeof {n} %zu\\n", sizeof({n}));' for n in ARG_STRUCTS + PART_STRUCTS]
+    for st in ARG_STRUCTS:
+        lines += [f'  printf("{st}.{n} %zu\\n", offsetof({st}, {n}));' for n, _ in getattr(mat_train, st)._fields_]
+    d = tmp_path_factory.mktemp("arg_structs")
+    src = d / "sz.hip"
     src.write_text(f'#include <cstdio>\n#include <cstddef>\n#include "{csrc}/mat_train_common.h"\n'
-                   f'int main() {{\n  printf("sizeof %zu\\n", sizeof(ActP));\n{lines}\n}}\n')
-    exe = tmp_path / "sz"
+                   'int main() {\n' + "\n".join(lines) + '\n}\n')
+    exe = d / "sz"
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O0", "--offload-arch=gfx950", str(src), "-o", str(exe)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout
-    got = {l.split()[0]: int(l.split()[1]) for l in out.strip().splitlines()}
-    want = {"sizeof": ctypes.sizeof(mat_train.ActP)}
-    want.update({n: getattr(mat_train.ActP, n).offset for n in names})
+    return {l.rsplit(" ", 1)[0]: int(l.rsplit(" ", 1)[1]) for l in out.strip().splitlines()}
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.parametrize("st", ARG_STRUCTS)
+def test_actor_arg_struct_matches_ctypes(c_struct_layout, st):
+    """EncP's, DecP's and ActP's ctypes mirrors against the C struct's size and EVERY field offset (array and nested
+    members at the member's own offset), plus the sizes of the structs they are built from."""
+    from mat_dcml_amd.ops import mat_train
+    cls = getattr(mat_train, st)
+    want = {f"sizeof {n}": ctypes.sizeof(getattr(mat_train, n)) for n in (st,) + PART_STRUCTS}
+    want.update({f"{st}.{n}": getattr(cls, n).offset for n, _ in cls._fields_})
+    got = {k: v for k, v in c_struct_layout.items() if k in want}
+    assert len(want) == len(cls._fields_) + 1 + len(PART_STRUCTS)
     assert got == want, (got, want)

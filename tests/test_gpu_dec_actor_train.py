@@ -186,7 +186,7 @@ class Case:
         try:
             v, rep = self.enc.forward(obs, idx=idx)
             logp, ent = self.act.forward(rep, actions, ava, idx=idx)
-            self.last_saves = (self.enc.ctx[3], self.act.ctx[5])
+            self.last_saves = (self.enc.ctx.saves, self.act.ctx.saves)
             drep = self.act.backward(self.w1, self.w3)
             assert drep.shape == rep.shape and float(drep.abs().max()) == 0
             self.enc.backward(drep, self.w2 if dv is None else dv)
