@@ -151,15 +151,19 @@ class MATTrainer:
         # Semi_Discrete, Continuous and, with MAT_DCML_AVAIL_CONT_TRAIN=fused and 3 <= action_dim <= 16,
         # Available_Continuous (their action-embedding backward is an MFMA weight-gradient product flushed like every
         # other weight gradient, csrc/mat_dec_ct.hip) — and MAT-Dec's shared actor with MAT_DCML_DEC_ACTOR_TRAIN=fused
-        # (csrc/mat_actor_ct.hip: the same flushes, obs_dim <= 16).  Available_Continuous without its switch (the
-        # default) or with another action_dim, and dec_actor without its switch, with per-agent actors or with wide
-        # observations, train through the hybrid path (self.fused is False, eager decoder) and make no such claim
+        # (csrc/mat_actor_ct.hip: the same flushes; obs_dim > 16 with MAT_DCML_DEC_ACTOR_WIDE_OBS=fused as well: the
+        # actor's own obs-embedding backward, same grad mode as the encoder's).  Available_Continuous without its switch
+        # (the default) or with another action_dim, and dec_actor without its switch(es) or with per-agent actors,
+        # train through the hybrid path (self.fused is False, eager decoder) and make no such claim
         self.obs_embed_grad = None
         if wide:
             enc = mat_train._state(m, self.device)[0]
             if getattr(enc, "emb", None) is None:
                 enc.emb = mat_train.ObsEmbed(m)
             self.obs_embed_grad = enc.emb.grad_mode
+            dec = mat_train._state(m, self.device)[1]
+            if isinstance(dec, mat_train.ActorFused):   # MAT-Dec: the actor's instance, built under the same setting
+                dec.obs_embed()
         self.nondeterministic_writer = None
         if mode != "private" or copies <= 0:
             self.nondeterministic_writer = f"gradient workspace (mode {mode}, {copies} copies): fp32 global atomics"
@@ -183,10 +187,11 @@ class MATTrainer:
         # sums per-workgroup partials in fixed order (tests/test_gpu_obs_embed_det.py), the Continuous action type
         # (MA-MuJoCo, tests/test_gpu_continuous_det.py) and Available_Continuous on the fused decoder kernels
         # (MAT_DCML_AVAIL_CONT_TRAIN=fused, 3 <= action_dim <= 16, tests/test_gpu_avail_cont_train.py) and MAT-Dec's
-        # shared actor on the fused actor kernels (MAT_DCML_DEC_ACTOR_TRAIN=fused, tests/test_gpu_dec_actor_train.py).
+        # shared actor on the fused actor kernels (MAT_DCML_DEC_ACTOR_TRAIN=fused, tests/test_gpu_dec_actor_train.py;
+        # wide observations with MAT_DCML_DEC_ACTOR_WIDE_OBS=fused, tests/test_gpu_dec_actor_wide.py).
         # The warning names the order-dependent writer of the opt-outs (MAT_DCML_GRAD_MODE=atomic,
-        # MAT_DCML_OBS_EMBED_GRAD=atomic); the hybrid path (Available_Continuous and dec_actor by default, per-agent or
-        # wide-observation actors always: eager decoder) is outside the claim and reports nothing here
+        # MAT_DCML_OBS_EMBED_GRAD=atomic); the hybrid path (Available_Continuous and dec_actor by default, per-agent
+        # actors always: eager decoder) is outside the claim and reports nothing here
         if getattr(args, "cuda_deterministic", False) and not self.deterministic and self.device.type == "cuda":
             import warnings
             warnings.warn("cuda_deterministic: this configuration's fused update is not bit-reproducible: "

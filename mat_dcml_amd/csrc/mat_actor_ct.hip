@@ -5,8 +5,10 @@
 // The actor is two stages the training kernels already hold, run back to back on one token tile with no attention, no
 // cross attention and no LDS in the forward:
 //  * LN(od) -> Linear(od, 64) -> GELU -> LN: the encoder's observation embedding and its ln (mat_embed_ct.h obs_ln /
-//    we_frags / embed_pre, always the in-kernel embedding: EncX{nullptr, nullptr}; the loops around them are those of
-//    enc_fwd_tile / enc_bwd_tile without the pre_in branches);
+//    we_frags / embed_pre; the loops around them are those of enc_fwd_tile / enc_bwd_tile).  obs_dim <= 16 embeds
+//    in-kernel (a constant EncX{nullptr, nullptr}); wider observations run the WIDE instantiations (the *_wide
+//    kernels and entry points), which take the pre-activation of obs_embed.hip as EncX.pre_in and hand d pre back
+//    through EncX.dpre_out — the encoder's pre_in branches, chosen at compile time here;
 //  * Linear(64, 64) -> GELU -> LN -> Linear(64, A) + the categorical / Normal statistics and masks: the decoder's
 //    action head (mat_head_ct.h head_fwd_ct / head_bwd_ct).
 // Both headers take the kernel argument ActP as it is (they read the fields it shares by name with EncP / DecP).  This
@@ -29,23 +31,29 @@ namespace {
 // ============================================================================================== forward
 // LOGITS (rollout, never with SAVE): the head's unmasked logits [tok][A] leave instead of log-prob / entropy — the
 // same embedding, W_2, LayerNorm and logit products as the learner's pass; masking and sampling stay with the caller
-template <bool SAVE, int MA, bool CONT, bool LOGITS>
-__device__ __forceinline__ void actor_fwd_tile(const ActP& a, char* smem, int seq0, int nseq) {
+//
+// WIDE (obs_dim > 16, compile time): the embedding pre-activation comes in as ex.pre_in, computed by the obs-embedding
+// GEMM kernels (obs_embed.hip) — no W_1 fragments and no LN_obs here; GELU, LayerNorm and the saves are the narrow
+// tile's.  The narrow instantiations take a constant EncX{nullptr, nullptr} and keep their instruction streams
+// (profiles/dec_actor_wide/README.md).
+template <bool SAVE, int MA, bool CONT, bool LOGITS, bool WIDE>
+__device__ __forceinline__ void actor_fwd_tile(const ActP& a, const EncX& ex, char* smem, int seq0, int nseq) {
   const Ctx c = make_ctx(a, smem, seq0, nseq);
   if (c.nseq <= 0) return;
   const int lane = c.lane, g = lane >> 4;
-  const EncX ex{nullptr, nullptr};
   CT xr[MAXRT];
   {
     bf16x8 W[4];
-    we_frags(a, W, lane);
+    if constexpr (!WIDE) we_frags(a, W, lane);
     const CT gam = ld_vec(a.ln0_g, lane), bet = ld_vec(a.ln0_b, lane);
 #pragma unroll
     for (int k = 0; k < MAXRT; ++k) {
       const int rt = c.wave + NW * k;
       if (rt < c.NT) {
         float oh[4], hat[4];
-        CT pre = embed_pre(a, ex, rt, W, oh, hat, c), xh;
+        CT pre, xh;
+        if constexpr (WIDE) pre = ld_gf(ex.pre_in, c.tok0, rt, c.NR, lane);
+        else pre = embed_pre(a, ex, rt, W, oh, hat, c);
         if (SAVE) {   // x-hat, GELU'(pre), rstd for the backward (which recomputes none of the embedding forward)
           CT gp;
           gelu_ct_both(pre, gp);
@@ -97,7 +105,12 @@ __device__ __forceinline__ void actor_fwd_tile(const ActP& a, char* smem, int se
 template <bool SAVE, int MA, bool CONT, bool LOGITS>
 __global__ __launch_bounds__(NTHR, FWD_WGPC) void mat_actor_fwd_ct(ActP a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS>(a, smem, s0, ns)));
+  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS, false>(a, EncX{nullptr, nullptr}, smem, s0, ns)));
+}
+template <bool SAVE, int MA, bool CONT, bool LOGITS>
+__global__ __launch_bounds__(NTHR, FWD_WGPC) void mat_actor_fwd_ct_wide(ActP a, EncX ex) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  FOR_TILES(a, (actor_fwd_tile<SAVE, MA, CONT, LOGITS, true>(a, ex, smem, s0, ns)));
 }
 #endif  // !MDL_CT_BWD_TU
 
@@ -109,8 +122,11 @@ __device__ __forceinline__ int actor_small_wg_slot0(const ActP& a) {
   return (MDL_SMALL_WG_VACC && a.A <= 2 && 10 + a.A + 1 <= VSLOTS) ? 9 - a.A : -1;
 }
 
-template <int MA, bool CONT>
-__device__ __forceinline__ void actor_bwd_tile(const ActP& a, char* smem, int seq0, int nseq, bool first) {
+//
+// WIDE (compile time): d pre leaves through ex.dpre_out (rows < NR only) for the obs-embedding backward kernels, which
+// own the W_1, b_1 and LN_obs gradients — no LDS staging, no slots 7-9 and no wgrad_g here; slots 5-6 flush as before.
+template <int MA, bool CONT, bool WIDE>
+__device__ __forceinline__ void actor_bwd_tile(const ActP& a, const EncX& ex, char* smem, int seq0, int nseq, bool first) {
   const Ctx c = make_ctx(a, smem, seq0, nseq, first);
   if (c.nseq <= 0) return;
   zero_pad_rows(c);
@@ -120,7 +136,27 @@ __device__ __forceinline__ void actor_bwd_tile(const ActP& a, char* smem, int se
   // ---------------- head backward: dx = d LN0 output; d W_2, d W_h2, their biases, the head LayerNorm, log_std
   head_bwd_ct<MA, CONT, false>(a, dx, c, actor_small_wg_slot0(a));
   // ---------------- embedding backward: x0 = LN0(GELU(pre)), pre = W_1 · LN_obs(obs) + b_1  (enc_bwd_tile)
-  {
+  if constexpr (WIDE) {
+    CT dlg, dlb;
+    ct_zero(dlg);
+    ct_zero(dlb);
+    const CT gam = ld_vec(a.ln0_g, lane);
+#pragma unroll
+    for (int k = 0; k < MAXRT; ++k) {
+      const int rt = c.wave + NW * k;
+      if (rt < c.NT) {
+        const bool ok = tok_ok(rt, c);
+        const CT xh = ct_unpack(ld_g(a.es.xh, c.tok0, rt, c.NR, lane)), egp = ct_unpack(ld_g(a.es.gp, c.tok0, rt, c.NR, lane));
+        CT de;
+        ln_bwd_ct(dx[k], xh, ld_tokf(a.es.rs, rt, c), gam, ok, de, dlg, dlb);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) de.v[i] *= egp.v[i];
+        st_gf(ex.dpre_out, c.tok0, rt, c.NR, de, lane);   // stores rows < NR only
+      }
+    }
+    flush_vec(dlg, c.g(a.d_ln0_g), 5, c);
+    flush_vec(dlb, c.g(a.d_ln0_b), 6, c);
+  } else {
     CT dlg, dlb, dbe;
     ct_zero(dlg);
     ct_zero(dlb);
@@ -190,7 +226,14 @@ template <int MA, bool CONT>
 __global__ __launch_bounds__(NTHR, WGPC) void mat_actor_bwd_ct(ActP a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   vacc_begin(a, smem);
-  FOR_TILES(a, (actor_bwd_tile<MA, CONT>(a, smem, s0, ns, it_ == 0)));
+  FOR_TILES(a, (actor_bwd_tile<MA, CONT, false>(a, EncX{nullptr, nullptr}, smem, s0, ns, it_ == 0)));
+  vacc_end(a, smem);
+}
+template <int MA, bool CONT>
+__global__ __launch_bounds__(NTHR, WGPC) void mat_actor_bwd_ct_wide(ActP a, EncX ex) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  vacc_begin(a, smem);
+  FOR_TILES(a, (actor_bwd_tile<MA, CONT, true>(a, ex, smem, s0, ns, it_ == 0)));
   vacc_end(a, smem);
 }
 #endif  // MDL_CT_BWD_TU
@@ -200,6 +243,12 @@ __global__ __launch_bounds__(NTHR, WGPC) void mat_actor_bwd_ct(ActP a) {
 // ============================================================================================== host API
 static bool actor_args_ok(const ActP* p) {
   return p->od >= 1 && p->od <= 16 && p->A >= 1 && p->A <= 64 && p->n_disc >= 0 && p->n_disc <= p->L &&
+         !(p->cont && p->n_disc != 0);
+}
+// the _wide entry points: obs_dim > 16 only with the pre-activation `pre_in` ([tok][64] f32 of the dense minibatch
+// order, obs_embed.hip); the kernels then read neither obs nor the W_1 / LN_obs fields
+static bool actor_args_ok_wide(const ActP* p, const float* pre_in) {
+  return pre_in && p->od >= 1 && p->A >= 1 && p->A <= 64 && p->n_disc >= 0 && p->n_disc <= p->L &&
          !(p->cont && p->n_disc != 0);
 }
 
@@ -224,11 +273,42 @@ MDL_API int mdl_mat_actor_fwd_ct(const ActP* p, int save, hipStream_t st) {
   if (p->A <= 16) return actor_fwd_ct<1, false>(p, save, st);
   return p->A <= 48 ? actor_fwd_ct<3, false>(p, save, st) : actor_fwd_ct<4, false>(p, save, st);
 }
+
+template <int MA, bool CONT>
+static int actor_fwd_ct_wide(const ActP* p, const EncX& ex, int save, hipStream_t st) {
+  return save ? launch_ct(mat_actor_fwd_ct_wide<true, MA, CONT, false>, p, true, st, ex)
+              : launch_ct(mat_actor_fwd_ct_wide<false, MA, CONT, false>, p, true, st, ex);
+}
+// the same passes on a pre-activation computed outside (any obs_dim); pre_in null: the in-kernel embedding above
+MDL_API int mdl_mat_actor_fwd_ct_wide(const ActP* p, const float* pre_in, int save, hipStream_t st) {
+  if (!pre_in) return mdl_mat_actor_fwd_ct(p, save, st);
+  if (!actor_args_ok_wide(p, pre_in)) return -1;
+  const EncX ex{pre_in, nullptr};
+  if (p->logits) {
+    if (save) return -1;
+    if (p->A <= 16) return launch_ct(mat_actor_fwd_ct_wide<false, 1, false, true>, p, true, st, ex);
+    return p->A <= 48 ? launch_ct(mat_actor_fwd_ct_wide<false, 3, false, true>, p, true, st, ex)
+                      : launch_ct(mat_actor_fwd_ct_wide<false, 4, false, true>, p, true, st, ex);
+  }
+  if (!p->act || !p->logp || !p->ent) return -1;
+  if (p->cont) return p->A <= 16 ? actor_fwd_ct_wide<1, true>(p, ex, save, st) : actor_fwd_ct_wide<4, true>(p, ex, save, st);
+  if (p->A <= 16) return actor_fwd_ct_wide<1, false>(p, ex, save, st);
+  return p->A <= 48 ? actor_fwd_ct_wide<3, false>(p, ex, save, st) : actor_fwd_ct_wide<4, false>(p, ex, save, st);
+}
 #else
 MDL_API int mdl_mat_actor_bwd_ct(const ActP* p, hipStream_t st) {
   if (!actor_args_ok(p) || !p->act || !p->dlogp || !p->dent || !p->sv_head || !p->hs.xh || !p->es.xh) return -1;
   if (p->cont) return p->A <= 16 ? launch_ct(mat_actor_bwd_ct<1, true>, p, false, st) : launch_ct(mat_actor_bwd_ct<4, true>, p, false, st);
   if (p->A <= 16) return launch_ct(mat_actor_bwd_ct<1, false>, p, false, st);
   return p->A <= 48 ? launch_ct(mat_actor_bwd_ct<3, false>, p, false, st) : launch_ct(mat_actor_bwd_ct<4, false>, p, false, st);
+}
+MDL_API int mdl_mat_actor_bwd_ct_wide(const ActP* p, const float* pre_in, float* dpre_out, hipStream_t st) {
+  if (!pre_in) return mdl_mat_actor_bwd_ct(p, st);
+  if (!actor_args_ok_wide(p, pre_in) || !dpre_out || !p->act || !p->dlogp || !p->dent || !p->sv_head || !p->hs.xh || !p->es.xh)
+    return -1;
+  const EncX ex{pre_in, dpre_out};
+  if (p->cont) return p->A <= 16 ? launch_ct(mat_actor_bwd_ct_wide<1, true>, p, false, st, ex) : launch_ct(mat_actor_bwd_ct_wide<4, true>, p, false, st, ex);
+  if (p->A <= 16) return launch_ct(mat_actor_bwd_ct_wide<1, false>, p, false, st, ex);
+  return p->A <= 48 ? launch_ct(mat_actor_bwd_ct_wide<3, false>, p, false, st, ex) : launch_ct(mat_actor_bwd_ct_wide<4, false>, p, false, st, ex);
 }
 #endif  // MDL_CT_BWD_TU

@@ -13,8 +13,9 @@
 //
 // obs_dim <= 16 runs in-kernel (LN_obs per lane, W_e on MFMA with a hi/lo split of the LN output); larger
 // observations (SMAC: 1288) come in as the embedding pre-activation `pre_in` computed by the obs-embedding GEMM
-// kernels (obs_embed.hip), and the backward hands d pre back through `dpre_out` (encoder only: the actor passes a
-// constant EncX{nullptr, nullptr}, so its copy of embed_pre holds no pre_in branch).
+// kernels (obs_embed.hip), and the backward hands d pre back through `dpre_out`.  The encoder branches on pre_in at
+// run time; the actor at compile time (its WIDE tiles read pre_in / write dpre_out, its narrow tiles pass a constant
+// EncX{nullptr, nullptr}, so their copy of embed_pre holds no pre_in branch).
 #pragma once
 #include "mat_train_ct.h"
 

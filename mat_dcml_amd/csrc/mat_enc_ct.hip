@@ -4,7 +4,7 @@
 // This file holds the encoder's own tiles (enc_fwd_tile / enc_bwd_tile), kernels and host API; the pieces of the
 // observation embedding (in-kernel for obs_dim <= 16, `pre_in` / `dpre_out` for wider observations: LN_obs, the W_e
 // fragments, the pre-activation) are mat_embed_ct.h, shared with the MAT-Dec actor (mat_actor_ct.hip), whose tiles
-// hold the same embedding loops as the two here without the pre_in branches.
+// hold the same embedding loops as the two here with the pre_in branches taken at compile time (its WIDE variant).
 //
 // LayerNorm: the two-pass form (mat_train_ct.h ln_fwd_ct), for this unit and its backward wrapper mat_enc_ct_bwd.hip.
 #define MDL_LN_ONEPASS 0

@@ -194,8 +194,10 @@ def refresh_packs(model):
     if supports(model) and not model.decoder.dec_actor:   # (MAT-Dec: the actor's one matrix is in the ModelPack)
         decoder_pack(model)
     if mat_train.encoder_supported(model):
-        enc, _, _ = mat_train._state(model, next(model.parameters()).device)
+        enc, dec, _ = mat_train._state(model, next(model.parameters()).device)
         enc.refresh_packs()
+        if mat_train.dec_actor_fused(model):   # MAT-Dec on wide observations: the actor's own W' pack
+            dec.refresh_packs()
 
 
 def set_sampling_key(model, seed: int, env0: int = 0):

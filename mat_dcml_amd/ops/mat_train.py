@@ -92,6 +92,8 @@ sig("mdl_mat_dec_fwd_ct", ctypes.POINTER(DecP), ctypes.c_int, ctypes.c_int, VP)
 sig("mdl_mat_dec_bwd_ct", ctypes.POINTER(DecP), ctypes.c_int, VP)
 sig("mdl_mat_actor_fwd_ct", ctypes.POINTER(ActP), ctypes.c_int, VP)
 sig("mdl_mat_actor_bwd_ct", ctypes.POINTER(ActP), VP)
+sig("mdl_mat_actor_fwd_ct_wide", ctypes.POINTER(ActP), VP, ctypes.c_int, VP)
+sig("mdl_mat_actor_bwd_ct_wide", ctypes.POINTER(ActP), VP, VP, VP)
 sig("mdl_grad_reduce", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP)
 sig("mdl_grad_reduce_norm", VP, VP, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP, VP)
 sig("mdl_grad_reduce_priv", VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, VP, VP)
@@ -123,13 +125,19 @@ class ObsEmbed:
     ``grad_mode``: how the backward's token reductions are summed.  ``"partials"`` (default): every workgroup stores
     its partial into ``Mp`` / ``up`` and one kernel adds them in index order — bitwise repeatable.  ``"atomic"``
     (``MAT_DCML_OBS_EMBED_GRAD=atomic``, read when the object is built): fp32 atomics, for A/B runs.  The partial
-    workspaces (SMAC: 22 MB) are allocated by the first backward, so rollout-only and eval processes never hold them."""
+    workspaces (SMAC: 22 MB) are allocated by the first backward, so rollout-only and eval processes never hold them.
 
-    def __init__(self, model):
+    ``pair``: the (LayerNorm, Linear) it serves — the encoder's ``obs_encoder`` by default, ``decoder.mlp[0:2]`` for
+    MAT-Dec's shared actor.  ``share``: another instance of the same width whose ``Mp`` / ``up`` partial workspace this
+    one uses too (the two run back to back on one stream, and every backward rewrites each partial it reads)."""
+
+    def __init__(self, model, pair=None, share=None):
         enc = model.encoder
         self.model = model
-        self.ln, self.lin = enc.obs_encoder[0], enc.obs_encoder[1]
-        self.od = enc.obs_dim
+        self.ln, self.lin = pair if pair is not None else (enc.obs_encoder[0], enc.obs_encoder[1])
+        self.od = self.lin.weight.shape[1]
+        if share is not None and share.od != self.od:
+            raise ValueError(f"ObsEmbed: shared partial workspace of width {share.od}, this embedding's is {self.od}")
         self.KS = (self.od + 31) // 32
         dev = self.lin.weight.device
         self.wpack = torch.empty(self.KS * 4 * 64 * 8, dtype=torch.bfloat16, device=dev)
@@ -139,8 +147,16 @@ class ObsEmbed:
         self.grad_mode = os.environ.get("MAT_DCML_OBS_EMBED_GRAD", "partials")
         if self.grad_mode not in ("partials", "atomic"):
             raise ValueError(f"MAT_DCML_OBS_EMBED_GRAD={self.grad_mode}: expected 'partials' or 'atomic'")
-        self.Mp = self.up = None
+        self._part = share._part if share is not None else {"Mp": None, "up": None}   # the partial workspace
         self.version = None
+
+    @property
+    def Mp(self):
+        return self._part["Mp"]
+
+    @property
+    def up(self):
+        return self._part["up"]
 
     def _args(self, N=0, x=None, pre=None, stat=None, dpre=None):
         xh = x if x is not None and x.dtype == torch.bfloat16 else None
@@ -173,8 +189,8 @@ class ObsEmbed:
     def backward(self, obs2d, stat, dpre):
         if self.grad_mode == "partials" and self.Mp is None:
             dev = self.M.device
-            self.Mp = torch.empty(OEB_SPLIT * 64 * 64 * ((self.od + 63) // 64), device=dev)
-            self.up = torch.empty(OEB_UBLK * 128, device=dev)
+            self._part["Mp"] = torch.empty(OEB_SPLIT * 64 * 64 * ((self.od + 63) // 64), device=dev)
+            self._part["up"] = torch.empty(OEB_UBLK * 128, device=dev)
         a = self._args(obs2d.shape[0], obs2d, None, stat, dpre)
         check(lib().mdl_obs_embed_bwd(ctypes.byref(a), kernels._stream()), "obs_embed_bwd")
 
@@ -364,6 +380,20 @@ def dec_actor_train_mode():
     return mode
 
 
+DEC_ACTOR_WIDE_ENV = "MAT_DCML_DEC_ACTOR_WIDE_OBS"
+
+
+def dec_actor_wide_obs_mode():
+    """How a fused shared actor (MAT_DCML_DEC_ACTOR_TRAIN=fused) takes observations wider than the in-kernel embedding,
+    read from MAT_DCML_DEC_ACTOR_WIDE_OBS at call time: ``hybrid`` (default: such models stay on the hybrid path) or
+    ``fused`` (csrc/obs_embed.hip computes the actor's embedding pre-activation and its gradients, the WIDE actor
+    kernels the rest: the whole update on HIP kernels, bit-reproducible).  Without the first switch it has no effect."""
+    mode = os.environ.get(DEC_ACTOR_WIDE_ENV, "hybrid")
+    if mode not in ("hybrid", "fused"):
+        raise ValueError(f"{DEC_ACTOR_WIDE_ENV}={mode}: expected 'hybrid' or 'fused'")
+    return mode
+
+
 def dec_actor_reasons(model):
     """Why a ``dec_actor`` model stays off the fused actor kernels: the switch, or one reason per condition they set
     beyond the shared gates (action_dim <= 64, semi_index == -1, the tiling)."""
@@ -374,9 +404,11 @@ def dec_actor_reasons(model):
     r = []
     if not dec.share_actor:
         r.append(f"dec_actor with per-agent actors (share_actor=False): {DEC_ACTOR_ENV}=fused takes the shared actor")
-    if model.encoder.obs_dim > MAX_FUSED_OBS:
+    wide_obs = dec_actor_wide_obs_mode()   # read (and validated) whatever the width
+    if model.encoder.obs_dim > MAX_FUSED_OBS and wide_obs != "fused":
         r.append(f"dec_actor with obs_dim {model.encoder.obs_dim} > {MAX_FUSED_OBS}: the fused actor kernels embed "
-                 f"at most {MAX_FUSED_OBS} observation features")
+                 f"at most {MAX_FUSED_OBS} observation features ({DEC_ACTOR_WIDE_ENV}=fused selects the "
+                 "obs-embedding kernels for the actor)")
     if model.action_type in AVAIL_CONT_TYPES:
         r.append("dec_actor with action_type Available_Continuous: the fused actor kernels take Discrete, "
                  "Semi_Discrete and Continuous")
@@ -439,6 +471,7 @@ class EncCtx(NamedTuple):
     hs: HSv
     es: HSv
     idx: Optional[torch.Tensor]
+    gathered: Optional[torch.Tensor] = None   # wide observations under idx: `obs` holds the dense rows obs[gathered]
 
 
 class DecCtx(NamedTuple):
@@ -466,6 +499,8 @@ class ActCtx(NamedTuple):
     hs: HSv
     es: HSv
     idx: Optional[torch.Tensor]
+    pre: Optional[torch.Tensor] = None    # wide observations: the embedding pre-activation and its LayerNorm
+    stat: Optional[torch.Tensor] = None   # statistics (obs then holds dense rows; idx serves act / ava only)
 
 
 # ------------------------------------------------------------------------------------------------- encoder
@@ -500,9 +535,13 @@ class EncoderFused:
         pack) on the CURRENT stream — see mat_fused.refresh_packs."""
         model_pack(self.model)
         if self.model.encoder.obs_dim > MAX_FUSED_OBS:
-            if getattr(self, "emb", None) is None:
-                self.emb = ObsEmbed(self.model)
-            self.emb.refresh()
+            self.obs_embed().refresh()
+
+    def obs_embed(self):
+        """The wide-observation embedding of ``encoder.obs_encoder`` (built on first use)."""
+        if getattr(self, "emb", None) is None:
+            self.emb = ObsEmbed(self.model)
+        return self.emb
 
     def forward(self, obs, save=True, idx=None):
         """obs (B, L, od) -> (v (B, L, n_obj), rep (B, L, 64) f32).  ``idx`` (int64 [B]): obs is the rollout
@@ -519,13 +558,11 @@ class EncoderFused:
         n_tok = B * L
         wide_bf16 = od > MAX_FUSED_OBS and (WIDE_OBS_BF16 or obs.dtype == torch.bfloat16)
         obs = (obs.to(torch.bfloat16) if wide_bf16 else obs.float()).contiguous()
-        pre = stat = None
+        pre = stat = gathered = None
         if od > MAX_FUSED_OBS:   # wide observations: embedding pre-activation from the obs-embedding kernel
             if idx is not None:  # (the wide embedding reads dense rows)
-                obs, idx = obs[idx].contiguous(), None
-            if getattr(self, "emb", None) is None:
-                self.emb = ObsEmbed(m)
-            pre, stat = self.emb.forward(obs.view(n_tok, od))
+                obs, idx, gathered = obs[idx].contiguous(), None, idx
+            pre, stat = self.obs_embed().forward(obs.view(n_tok, od))
         rep = torch.empty(B, L, 64, device=dev)
         v = torch.empty(B, L, m.n_objective, device=dev)
         p = self.p
@@ -550,7 +587,8 @@ class EncoderFused:
             p.hs, p.es = HSv(), HSv()
         check(lib().mdl_mat_enc_fwd_ct(ctypes.byref(p), _ptr(pre), m.n_block, int(save), kernels._stream()), "mat_enc_fwd")
         self.ctx = EncCtx(obs=obs, rep=rep, v=v, saves=saves, svs=[Sv.from_buffer_copy(p.sv[i]) for i in range(m.n_block)],
-                          pre=pre, stat=stat, hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx)
+                          pre=pre, stat=stat, hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx,
+                          gathered=gathered)
         return v, rep
 
     def backward(self, drep, dv):
@@ -740,17 +778,45 @@ class ActorFused:
             ectx = getattr(self.enc, "ctx", None)
             if ectx is None:
                 raise RuntimeError("ActorFused.forward: no observations (pass obs=, or run the encoder forward first)")
-            obs, eidx = ectx.obs, ectx.idx
+            obs = ectx.obs
+            eidx = ectx.idx if ectx.gathered is None else ectx.gathered
             if (eidx is None) != (idx is None) or (idx is not None and eidx.data_ptr() != idx.data_ptr()):
                 raise RuntimeError("ActorFused.forward: the encoder's forward read other rows (idx differs)")
-        obs = obs.float().contiguous()
-        if obs.shape[-1] > MAX_FUSED_OBS:
-            raise RuntimeError(f"ActorFused: obs_dim {obs.shape[-1]} > {MAX_FUSED_OBS}")
-        return obs
+            if ectx.gathered is not None:   # wide observations: the encoder's dense rows obs[idx], already converted
+                idx = None
+        od = obs.shape[-1]
+        if od <= MAX_FUSED_OBS:
+            return obs.float().contiguous()
+        if dec_actor_wide_obs_mode() != "fused":
+            raise RuntimeError(f"ActorFused: obs_dim {od} > {MAX_FUSED_OBS} ({DEC_ACTOR_WIDE_ENV}=fused selects the "
+                               "obs-embedding kernels)")
+        # wide observations: dense rows for csrc/obs_embed.hip, bf16 on the terms of EncoderFused.forward
+        if idx is not None:
+            obs = obs[idx]
+        wide_bf16 = WIDE_OBS_BF16 or obs.dtype == torch.bfloat16
+        return (obs.to(torch.bfloat16) if wide_bf16 else obs.float()).contiguous()
+
+    def obs_embed(self):
+        """The wide-observation embedding of the actor's ``mlp[0:2]`` (built on first use); its partial workspace is the
+        encoder's instance's (one stream, back to back)."""
+        if getattr(self, "emb", None) is None:
+            a = self.model.decoder.mlp
+            share = self.enc.obs_embed() if self.enc is not None and \
+                self.model.encoder.obs_dim == a[1].weight.shape[1] else None
+            self.emb = ObsEmbed(self.model, (a[0], a[1]), share=share)
+        return self.emb
+
+    def refresh_packs(self):
+        """The actor's version-keyed pack beyond the shared ModelPack (the wide-observation W' pack) on the CURRENT
+        stream — see mat_fused.refresh_packs."""
+        if self.model.decoder.mlp[1].weight.shape[1] > MAX_FUSED_OBS:
+            self.obs_embed().refresh()
 
     def forward(self, rep, actions, ava=None, save=True, idx=None, obs=None):
         """(logp, ent) of the stored actions.  ``rep`` gives the minibatch shape only; ``idx`` (int64 [B]): obs / actions /
-        ava are the rollout buffer's (N, L, .) rows, read through idx in-kernel."""
+        ava are the rollout buffer's (N, L, .) rows, read through idx in-kernel.  Wide observations (obs_dim > 16, the
+        gate open): their rows are gathered to dense ones for csrc/obs_embed.hip, whose pre-activation the WIDE kernel
+        reads; actions / ava still go through idx."""
         m = self.model
         self._build()
         B, L = rep.shape[:2]
@@ -760,17 +826,23 @@ class ActorFused:
         A = m.action_dim
         nact = nlp = A if self.cont else 1
         nrow = B if idx is None else actions.shape[0]
-        if obs.shape[0] != nrow or obs.shape[1] != L:
-            raise ValueError(f"observations {tuple(obs.shape)}: expected ({nrow}, {L}, od)")
+        od = obs.shape[-1]
+        wide = od > MAX_FUSED_OBS
+        if obs.shape[0] != (B if wide else nrow) or obs.shape[1] != L:
+            raise ValueError(f"observations {tuple(obs.shape)}: expected ({B if wide else nrow}, {L}, od)")
         act = actions.reshape(nrow, L, nact).float().contiguous()
         ava_c = ava.float().contiguous() if (ava is not None and not self.cont) else None
         if ava_c is not None and ava_c.numel() != nrow * L * A:
             raise ValueError(f"available actions {tuple(ava.shape)}: expected ({nrow}, {L}, {A})")
         logp = torch.empty(B, L, nlp, device=dev)
         ent = torch.empty(B, L, nlp, device=dev)
-        self._geom(B, L, obs.shape[-1])
+        pre = stat = None
+        if wide:
+            pre, stat = self.obs_embed().forward(obs.view(n_tok, od))
+        self._geom(B, L, od)
         p = self.p
-        p.obs, p.act, p.ava, p.logp, p.ent = obs.data_ptr(), act.data_ptr(), _ptr(ava_c), logp.data_ptr(), ent.data_ptr()
+        p.obs = None if wide else obs.data_ptr()   # (the WIDE kernels read pre, never obs)
+        p.act, p.ava, p.logp, p.ent = act.data_ptr(), _ptr(ava_c), logp.data_ptr(), ent.data_ptr()
         p.logits, p.dlogp, p.dent, p.sidx = None, None, None, _ptr(idx)
         saves = []
         if save:
@@ -782,9 +854,13 @@ class ActorFused:
             p.es = HSv(sv[3].data_ptr(), sv[4].data_ptr(), rs[1].data_ptr())
         else:
             p.sv_head, p.hs, p.es = None, HSv(), HSv()
-        check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), int(save), kernels._stream()), "mat_actor_fwd")
+        if wide:
+            check(lib().mdl_mat_actor_fwd_ct_wide(ctypes.byref(p), pre.data_ptr(), int(save), kernels._stream()),
+                  "mat_actor_fwd_wide")
+        else:
+            check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), int(save), kernels._stream()), "mat_actor_fwd")
         self.ctx = ActCtx(rep=rep, act=act, ava=ava_c, logp=logp, ent=ent, saves=saves, obs=obs, head=p.sv_head,
-                          hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx)
+                          hs=HSv.from_buffer_copy(p.hs), es=HSv.from_buffer_copy(p.es), idx=idx, pre=pre, stat=stat)
         return logp, ent
 
     @torch.no_grad()
@@ -794,14 +870,20 @@ class ActorFused:
         self._build()
         obs = self._obs(obs, None)
         B, L, od = obs.shape
+        wide = od > MAX_FUSED_OBS
+        pre = self.obs_embed().forward(obs.view(B * L, od))[0] if wide else None
         out = torch.empty(B, L, m.action_dim, device=obs.device)
         self._geom(B, L, od, spread=True)
         p = self.p
-        p.obs, p.act, p.ava, p.logp, p.ent, p.logits = obs.data_ptr(), None, None, None, None, out.data_ptr()
+        p.obs, p.act, p.ava, p.logp, p.ent, p.logits = None if wide else obs.data_ptr(), None, None, None, None, out.data_ptr()
         p.dlogp, p.dent, p.sidx, p.sv_head, p.hs, p.es = None, None, None, None, HSv(), HSv()
         p.g_delta, p.g_stride, p.g_copies, p.g_mode = 0, 0, 0, 0
         try:
-            check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), 0, kernels._stream()), "mat_actor_fwd")
+            if wide:
+                check(lib().mdl_mat_actor_fwd_ct_wide(ctypes.byref(p), pre.data_ptr(), 0, kernels._stream()),
+                      "mat_actor_fwd_wide")
+            else:
+                check(lib().mdl_mat_actor_fwd_ct(ctypes.byref(p), 0, kernels._stream()), "mat_actor_fwd")
         finally:
             p.logits = None
         return out
@@ -814,15 +896,25 @@ class ActorFused:
             raise RuntimeError("ActorFused.backward: the forward saved nothing (save=False)")
         self._build()
         B, L = rep.shape[:2]
-        self._geom(B, L, obs.shape[-1])
+        od = obs.shape[-1]
+        wide = x.pre is not None
+        self._geom(B, L, od)
         p = self.p
         dlogp = dlogp.reshape(-1).float().contiguous()
         dent = dent.reshape(-1).float().contiguous()
-        p.obs, p.act, p.ava, p.sidx = obs.data_ptr(), x.act.data_ptr(), _ptr(x.ava), _ptr(x.idx)
+        p.obs, p.act, p.ava, p.sidx = None if wide else obs.data_ptr(), x.act.data_ptr(), _ptr(x.ava), _ptr(x.idx)
         p.logp, p.ent, p.logits = x.logp.data_ptr(), x.ent.data_ptr(), None
         p.dlogp, p.dent, p.sv_head, p.hs, p.es = dlogp.data_ptr(), dent.data_ptr(), x.head, x.hs, x.es
         _set_workspace(p, m, B, p.SQ)
-        check(lib().mdl_mat_actor_bwd_ct(ctypes.byref(p), kernels._stream()), "mat_actor_bwd")
+        if wide:
+            # d pre from the WIDE kernel, then W_1 / b_1 / LN_obs gradients from the obs-embedding backward, added
+            # straight into .grad like the encoder's: the actor's gradients are complete when this returns
+            dpre = torch.empty_like(x.pre)
+            check(lib().mdl_mat_actor_bwd_ct_wide(ctypes.byref(p), x.pre.data_ptr(), dpre.data_ptr(), kernels._stream()),
+                  "mat_actor_bwd_wide")
+            self.emb.backward(obs.view(-1, od), x.stat, dpre)
+        else:
+            check(lib().mdl_mat_actor_bwd_ct(ctypes.byref(p), kernels._stream()), "mat_actor_bwd")
         # the actor does not read rep: d rep is identically zero (one cached tensor per shape, never written)
         z = self._zero
         if z is None or z.shape != rep.shape or z.device != rep.device:

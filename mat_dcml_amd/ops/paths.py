@@ -62,6 +62,8 @@ def kernel_report(runner) -> dict:
         # MAT-Dec (dec_actor): the rollout is one pass of the fused actor forward, and it is the learner's decoder stage
         actor = bool(getattr(getattr(m, "decoder", None), "dec_actor", False))
         out["decode"] = _hip("mat_actor_fwd" if actor else "mat_decode", reason or mat_fused.unsupported_reasons(m))
+        if actor and out["decode"].startswith("hip:") and m.encoder.obs_dim > mat_train.MAX_FUSED_OBS:
+            out["decode"] += "+obs_embed_fwd"   # wide observations: the actor's pre-activation from csrc/obs_embed.hip
         if not actor and hasattr(m, "_mdl_decode_path") and out["decode"].startswith("hip:"):   # set by the last decode call
             out["decode"] += f"[{m._mdl_decode_path}]"
         tr = getattr(runner, "trainer", None)
