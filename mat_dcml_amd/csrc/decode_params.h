@@ -48,6 +48,10 @@ struct DecParams {
                          // pack, ops/mat_train.ModelPack): the one-wave decode (mat_decode_wave.hip); null: not used
 };
 
+// a masked logit is -1e10 (transformer_act.py:8-22): anything at or below this is one.  The sampling heads clamp a
+// draw above the rounded CDF's last edge to the last action whose logit is above it
+constexpr float MASKED_BELOW = -5e9f;
+
 // in-kernel sampling noise: one Philox block per (global env, row, call counter, purpose); purpose 0 = the categorical
 // uniform (x) and the Normal draws of dims 0, 1 (Box-Muller of y, z); purpose 1 + k = dims 2 + 2k, 3 + 2k
 __device__ __forceinline__ float draw_u(const DecParams& p, int env, int row) {

@@ -237,13 +237,15 @@ __device__ __forceinline__ int sample_small(const float* lgr, int AD, const floa
   if (!det) {
     const float inv = 1.f / se;
     float cdf = 0.f;
-    int cnt = 0;
+    int cnt = 0, last = -1;
 #pragma unroll
     for (int a = 0; a < SMALL_AD; ++a) {
       cdf += e[a] * inv;
       cnt += (a < AD) & (cdf < uu);
+      last = (a < AD && l[a] > MASKED_BELOW) ? a : last;
     }
-    act = min(cnt, AD - 1);
+    // a draw above the rounded CDF's last edge takes the last AVAILABLE action (the CDF is flat over masked ones)
+    act = min(cnt, last < 0 ? AD - 1 : last);
   }
   la = l[0];
 #pragma unroll
@@ -389,12 +391,14 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
       act = amax;
       if (!p.deterministic) {
         float cdf = 0.f;
-        int cnt = 0;
+        int cnt = 0, last = -1;
         for (int a = 0; a < AD; ++a) {
-          cdf += __expf(((av && av[a] == 0.f) ? -1e10f : lg[a]) - lse);
+          const bool masked = av && av[a] == 0.f;
+          cdf += __expf((masked ? -1e10f : lg[a]) - lse);
           cnt += cdf < uu;
+          last = masked ? last : a;
         }
-        act = min(cnt, AD - 1);
+        act = min(cnt, last < 0 ? AD - 1 : last);   // (the last available action: see sample_small)
       }
       la = (av && av[act] == 0.f) ? -1e10f : lg[act];
     }
@@ -821,7 +825,8 @@ __global__ __launch_bounds__(256, 1) void mat_decode_kernel(DecParams p) {
           if (!p.deterministic) {   // inverse CDF: the number of actions whose running probability is below u
             const float cdf = wave_incl_scan(aok ? __expf(l - lse) : 0.f, lane);
             const float uu = RU[li];
-            act = min((int)__popcll((unsigned long long)__ballot(aok && cdf < uu)), AD - 1);
+            const unsigned long long avm = (unsigned long long)__ballot(aok && l > MASKED_BELOW);
+            act = min((int)__popcll((unsigned long long)__ballot(aok && cdf < uu)), avm ? 63 - __clzll(avm) : AD - 1);
           }
           act = __builtin_amdgcn_readfirstlane(act);
           const float la = __shfl(l, act, 64);
@@ -908,6 +913,29 @@ MDL_API int mdl_mat_decode_geometry(int NB, int L, int B) {
   return mat_decode_lds_bytes(NB, 1, 16, L) <= 160 * 1024 ? 1 | (16 << 8) : 0;
 }
 
+// What the 4-wave launch stages in LDS next to the KV caches: bit 0 = the per-row inputs (MAT_DCML_DECODE_STAGE=0
+// disables), bit 1 = precomputed cross-attention queries when they fit as well (MAT_DCML_DECODE_Q2PRE=0 disables);
+// -1 when the caches alone do not fit.  *lds_out = the launch's dynamic LDS bytes.
+static int decode_4wave_plan(const DecParams* p, int NB, size_t* lds_out) {
+  size_t lds = mat_decode_lds_bytes(NB, p->epw, p->rmax, p->L);
+  if (lds > 160 * 1024) return -1;
+  static const bool stage_ok = [] { const char* e = getenv("MAT_DCML_DECODE_STAGE"); return !(e && e[0] == '0'); }();
+  const size_t sb = mat_decode_stage_bytes(p->epw, p->L, p->act_dim, p->n_tok);
+  const bool stage = stage_ok && lds + sb <= 160 * 1024 && (p->rep != nullptr);
+  if (stage) lds += sb;
+  static const bool q2_ok = [] { const char* e = getenv("MAT_DCML_DECODE_Q2PRE"); return !(e && e[0] == '0'); }();
+  const size_t q2b = (size_t)NB * (p->L + 16) * 64 * 2;
+  const bool q2pre = q2_ok && lds + q2b <= 160 * 1024 && p->rep != nullptr;
+  if (q2pre) lds += q2b;
+  if (lds_out) *lds_out = lds;
+  return (stage ? 1 : 0) | (q2pre ? 2 : 0);
+}
+// the plan of the 4-wave launch mdl_mat_decode would make for these parameters (host only; tests, path reports)
+MDL_API int mdl_decode_4wave_plan(const DecParams* p, int NB) {
+  if (NB < 1 || NB > 3 || p->epw != 1 || p->L < 1) return -1;
+  return decode_4wave_plan(p, NB, nullptr);
+}
+
 MDL_API int mdl_mat_decode(const DecParams* p, int NB, hipStream_t st) {
   const int epw = p->epw;
   if (epw != 1 || p->act_dim > 64 || p->act_dim < 1) return -1;
@@ -920,20 +948,13 @@ MDL_API int mdl_mat_decode(const DecParams* p, int NB, hipStream_t st) {
     const int r = mdl_decode_wave(p, NB, st);
     if (r <= 0) return r;
   }
-  size_t lds = mat_decode_lds_bytes(NB, epw, p->rmax, p->L);
-  if (lds > 160 * 1024) return -2;
   const int grid = (p->B + epw - 1) / epw;
-  // stage the per-row inputs in LDS when they fit next to the KV caches (MAT_DCML_DECODE_STAGE=0 disables)
   DecParams q = *p;
-  static const bool stage_ok = [] { const char* e = getenv("MAT_DCML_DECODE_STAGE"); return !(e && e[0] == '0'); }();
-  const size_t sb = mat_decode_stage_bytes(epw, p->L, p->act_dim, p->n_tok);
-  q.stage = stage_ok && lds + sb <= 160 * 1024 && (p->rep != nullptr);
-  if (q.stage) lds += sb;
-  // precomputed cross-attention queries (MAT_DCML_DECODE_Q2PRE=0 disables) when they fit as well
-  static const bool q2_ok = [] { const char* e = getenv("MAT_DCML_DECODE_Q2PRE"); return !(e && e[0] == '0'); }();
-  const size_t q2b = (size_t)NB * (p->L + 16) * 64 * 2;
-  q.q2pre = q2_ok && lds + q2b <= 160 * 1024 && p->rep != nullptr;
-  if (q.q2pre) lds += q2b;
+  size_t lds = 0;
+  const int plan = decode_4wave_plan(p, NB, &lds);
+  if (plan < 0) return -2;
+  q.stage = plan & 1;
+  q.q2pre = (plan >> 1) & 1;
   p = &q;
 #define MDL_DECODE_LAUNCH(NB_, STG_)                                                                            \
   hipFuncSetAttribute((const void*)mat_decode_kernel<NB_, STG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \

@@ -505,13 +505,15 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
         const float uu = rdlane(i < 64 ? nz.U[0] : i < 128 ? nz.U[1] : nz.U[2], i & 63);
         const float inv = 1.f / se;
         float cdf = 0.f;
-        int cnt = 0;
+        int cnt = 0, last = -1;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
           cdf += e[a] * inv;
           cnt += (a < A) & (cdf < uu);
+          last = (a < A && l[a] > MASKED_BELOW) ? a : last;
         }
-        act = min(cnt, A - 1);
+        // a draw above the rounded CDF's last edge takes the last AVAILABLE action (the CDF is flat over masked ones)
+        act = min(cnt, last < 0 ? A - 1 : last);
       }
       float la = l[0];
 #pragma unroll
@@ -543,7 +545,8 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
       if (!det) {   // inverse CDF: the number of actions whose running probability is below u
         const float cdf = wv_incl_scan(aok ? __expf(l - lse) : 0.f, lane);
         const float uu = rdlane(i < 64 ? nz.U[0] : i < 128 ? nz.U[1] : nz.U[2], i & 63);
-        act = min((int)__popcll((unsigned long long)__ballot(aok && cdf < uu)), A - 1);
+        const unsigned long long avm = (unsigned long long)__ballot(aok && l > MASKED_BELOW);   // available actions
+        act = min((int)__popcll((unsigned long long)__ballot(aok && cdf < uu)), avm ? 63 - __clzll(avm) : A - 1);
       }
       act = __builtin_amdgcn_readfirstlane(act);
       a_out = (float)act;

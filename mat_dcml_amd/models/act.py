@@ -52,7 +52,10 @@ def _cat_sample(logit, u, deterministic):
         a = logp_all.argmax(-1)
     else:
         cdf = torch.cumsum(logp_all.exp(), -1)
-        a = (cdf < u.unsqueeze(-1)).sum(-1).clamp(max=logit.shape[-1] - 1)
+        # a draw above the rounded CDF's last edge (u01_open's top value is 1.0 in fp32) takes the last AVAILABLE
+        # action: the CDF is flat over the masked actions behind it, so the plain count would land on a masked one
+        last = logit.shape[-1] - 1 - (logit > 0.5 * MASK_LOGIT).flip(-1).float().argmax(-1)
+        a = torch.minimum((cdf < u.unsqueeze(-1)).sum(-1), last)
     return a, logp_all.gather(-1, a.unsqueeze(-1)).squeeze(-1)
 
 

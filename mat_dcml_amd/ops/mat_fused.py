@@ -36,6 +36,7 @@ sig("mdl_mat_decode", ctypes.POINTER(DecParams), i32, vp)
 sig("mdl_mat_decode_geometry", i32, i32, i32)
 sig("mdl_decode_wave_plan", ctypes.POINTER(DecParams), i32)
 sig("mdl_decode_spec_plan", ctypes.POINTER(DecParams), i32)
+sig("mdl_decode_4wave_plan", ctypes.POINTER(DecParams), i32)
 sig("mdl_decode_spec_enable", i32)
 sig("mdl_decode_spec_layout", i32)
 
@@ -285,8 +286,7 @@ def decode(model, rep, ava=None, deterministic=False, stride=1, rand=None):
                     avail, P(pk.get("qkv0")).value, 0, int(getattr(model, "_mdl_env0", 0)) & 0xFFFFFFFF,
                     P(pk.get("hfold")).value, P(pk.get("wfa") if WAVE_DECODE else None).value)
     if _spec_set[0] != SPEC_DECODE:
-        lib().mdl_decode_spec_enable(int(SPEC_DECODE))
-        _spec_set[0] = SPEC_DECODE
+        set_spec_enabled(SPEC_DECODE)
     # the path report (two plan queries + formatting) once per call shape, not per rollout step
     pkey = (B, L, A, model.n_block, int(bool(deterministic)), int(stride), cont, avail, gen, rand is not None,
             ava is not None, WAVE_DECODE, SPEC_DECODE, id(pk))
@@ -295,6 +295,13 @@ def decode(model, rep, ava=None, deterministic=False, stride=1, rand=None):
         model._mdl_decode_path_key = pkey
     check(lib().mdl_mat_decode(ctypes.byref(prm), model.n_block, kernels._stream()), "mat_decode")
     return out_a, out_lp
+
+
+def set_spec_enabled(on):
+    """Set the library's speculative-path switch and remember it, so ``decode`` sets it again only when
+    ``SPEC_DECODE`` differs."""
+    lib().mdl_decode_spec_enable(int(bool(on)))
+    _spec_set[0] = bool(on)
 
 
 _GEO = {}   # mdl_mat_decode_geometry results (a pure function of its arguments)
