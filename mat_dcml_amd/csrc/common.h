@@ -181,4 +181,6 @@ __device__ __forceinline__ float gelu_erf_both(float x, float& grad) {
   return x * cdf;
 }
 
+constexpr float HALF_LOG_2PI = 0.91893853320467274f;   // the Normal log-prob / entropy constant of every head
+
 }  // namespace mdl

@@ -1,4 +1,4 @@
-// Kernel arguments and sampling-noise helpers shared by the two rollout-decode kernels:
+// Kernel arguments shared by the two rollout-decode kernels (how a row is sampled: decode_sample.h):
 //   * mat_decode.hip      — 4 waves per env, every decode mode (stride blocks, continuous heads, long L);
 //   * mat_decode_wave.hip — ONE wave per env for one-row token passes (the rollout hot path), no barriers.
 // Reference semantics: mat_src/mat/algorithms/utils/transformer_act.py:76-99 (autoregressive sampling),
@@ -47,25 +47,6 @@ struct DecParams {
   const bf16_t* wfa;     // [10*NB+1][4096] decoder weights as token-on-lane A fragments (the training kernels' "fa"
                          // pack, ops/mat_train.ModelPack): the one-wave decode (mat_decode_wave.hip); null: not used
 };
-
-// a masked logit is -1e10 (transformer_act.py:8-22): anything at or below this is one.  The sampling heads clamp a
-// draw above the rounded CDF's last edge to the last action whose logit is above it
-constexpr float MASKED_BELOW = -5e9f;
-
-// in-kernel sampling noise: one Philox block per (global env, row, call counter, purpose); purpose 0 = the categorical
-// uniform (x) and the Normal draws of dims 0, 1 (Box-Muller of y, z); purpose 1 + k = dims 2 + 2k, 3 + 2k
-__device__ __forceinline__ float draw_u(const DecParams& p, int env, int row) {
-  const mdl::u4 r = mdl::philox4x32_10(p.genv0 + (uint32_t)env, (uint32_t)row, p.rctr, (uint32_t)mdl::P_POLICY, p.rk0, p.rk1);
-  return mdl::u01_open_f(r.x);
-}
-__device__ __forceinline__ float draw_n(const DecParams& p, int env, int row, int a) {
-  const int k = a >> 1;
-  const mdl::u4 r = mdl::philox4x32_10(p.genv0 + (uint32_t)env, (uint32_t)row, p.rctr, (uint32_t)(mdl::P_POLICY + k),
-                                       p.rk0, p.rk1);
-  const uint32_t b0 = k == 0 ? r.y : r.x, b1 = k == 0 ? r.z : r.y;
-  const float rad = sqrtf(-2.f * __logf(mdl::u01_open_f(b0))), th = 6.283185307179586f * mdl::u01_open_f(b1);
-  return (a & 1) ? rad * __sinf(th) : rad * __cosf(th);
-}
 
 // One-wave decode (mat_decode_wave.hip): 0 = launched, 1 = this configuration is not on its path (the caller runs
 // the 4-wave kernel), < 0 = launch error.

@@ -27,7 +27,7 @@
 // of phase D and the mask / draws of the head phase were first-touch loads on the critical path); outputs are
 // actions and log-probs (B, L).  Numerics: bf16 MFMA operands, f32 accumulation, f32 LayerNorm / softmax / log-softmax.
 #include "tile.h"
-#include "decode_params.h"
+#include "decode_sample.h"
 #include <cstdlib>
 
 using namespace mdl;
@@ -202,29 +202,14 @@ __device__ __forceinline__ void attention_mfma(const bf16_t* KV, int rowK, int r
   *(uint2*)(xa + 16) = make_uint2(pk2f(o1[0] * il, o1[1] * il), pk2f(o1[2] * il, o1[3] * il));
 }
 
-// inclusive prefix sum over the 64 lanes: DPP row_shr 1, 2, 4, 8 within each 16-lane row (zero fill), then the
-// totals of the lower rows (3 readlanes) — VALU only, no ds_bpermute round trips
-__device__ __forceinline__ float wave_incl_scan(float x, int lane) {
-  x += dppf<0x111>(x);
-  x += dppf<0x112>(x);
-  x += dppf<0x114>(x);
-  x += dppf<0x118>(x);
-  const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 15));
-  const float t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 31));
-  const float t2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 47));
-  const int r = lane >> 4;
-  return x + ((r >= 1 ? t0 : 0.f) + (r >= 2 ? t1 : 0.f) + (r >= 3 ? t2 : 0.f));
-}
-
 // categorical sample over <= 4 register logits (every lane of the row computes it alike): availability mask,
 // inverse-CDF draw (argmax when deterministic); returns the action, its masked logit and the log-sum-exp
 constexpr int SMALL_AD = 4;
-#define SMALL_AD_ 4
 __device__ __forceinline__ int sample_small(const float* lgr, int AD, const float* av, float uu, bool det, float& la,
                                             float& lse) {
   float l[SMALL_AD];
 #pragma unroll
-  for (int a = 0; a < SMALL_AD; ++a) l[a] = a < AD ? ((av && av[a] == 0.f) ? -1e10f : lgr[a]) : -INFINITY;
+  for (int a = 0; a < SMALL_AD; ++a) l[a] = a < AD ? ((av && av[a] == 0.f) ? MASK_LOGIT : lgr[a]) : -INFINITY;
   float mx = l[0];
   int amax = 0;
 #pragma unroll
@@ -322,7 +307,7 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
     int cat = -1;   // Available_Continuous: the categorical choice over logits 0, 1 (every lane of the row alike)
     if (p.avail_cont) {
       const float* av = p.ava ? (stage ? AVA + li * AD : p.ava + oi * AD) : nullptr;
-      const float l0 = (av && av[0] == 0.f) ? -1e10f : lg[0], l1 = (av && av[1] == 0.f) ? -1e10f : lg[1];
+      const float l0 = (av && av[0] == 0.f) ? MASK_LOGIT : lg[0], l1 = (av && av[1] == 0.f) ? MASK_LOGIT : lg[1];
       const float mx = fmaxf(l0, l1), lse = mx + __logf(__expf(l0 - mx) + __expf(l1 - mx));
       if (p.deterministic) cat = l1 > l0 ? 1 : 0;
       else {
@@ -342,7 +327,7 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
         if (q == 0) {
           const float z = (x - mean_a) / sd;
           p.out_a[oi * AD + a] = x;
-          p.out_lp[cat >= 0 ? oi * (AD - 1) + a - 1 : oi * AD + a] = -0.5f * z * z - __logf(sd) - 0.91893853320467274f;
+          p.out_lp[cat >= 0 ? oi * (AD - 1) + a - 1 : oi * AD + a] = -0.5f * z * z - __logf(sd) - HALF_LOG_2PI;
         }
       }
 #pragma unroll
@@ -382,11 +367,11 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
       float mx = -INFINITY;
       int amax = 0;
       for (int a = 0; a < AD; ++a) {
-        const float l = (av && av[a] == 0.f) ? -1e10f : lg[a];
+        const float l = (av && av[a] == 0.f) ? MASK_LOGIT : lg[a];
         if (l > mx) { mx = l; amax = a; }
       }
       float se = 0.f;
-      for (int a = 0; a < AD; ++a) se += __expf(((av && av[a] == 0.f) ? -1e10f : lg[a]) - mx);
+      for (int a = 0; a < AD; ++a) se += __expf(((av && av[a] == 0.f) ? MASK_LOGIT : lg[a]) - mx);
       lse = mx + __logf(se);
       act = amax;
       if (!p.deterministic) {
@@ -394,13 +379,13 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
         int cnt = 0, last = -1;
         for (int a = 0; a < AD; ++a) {
           const bool masked = av && av[a] == 0.f;
-          cdf += __expf((masked ? -1e10f : lg[a]) - lse);
+          cdf += __expf((masked ? MASK_LOGIT : lg[a]) - lse);
           cnt += cdf < uu;
           last = masked ? last : a;
         }
         act = min(cnt, last < 0 ? AD - 1 : last);   // (the last available action: see sample_small)
       }
-      la = (av && av[act] == 0.f) ? -1e10f : lg[act];
+      la = (av && av[act] == 0.f) ? MASK_LOGIT : lg[act];
     }
     if (q == 0) {
       p.out_a[oi] = (float)act;
@@ -414,7 +399,7 @@ __device__ __forceinline__ void head_phase(const DecParams& p, const float* H1, 
     const float x = p.deterministic ? mean_a : mean_a + sd * (stage ? RN[li * AD + a] : p.gen ? draw_n(p, env, i, a) : p.rnd_n[oi * AD + a]);
     const float z = (x - mean_a) / sd;
     p.out_a[oi] = x;
-    p.out_lp[oi] = -0.5f * z * z - __logf(sd) - 0.91893853320467274f;
+    p.out_lp[oi] = -0.5f * z * z - __logf(sd) - HALF_LOG_2PI;
     PEND[m * L + i] = -1;
   }
 }
@@ -484,14 +469,12 @@ __global__ __launch_bounds__(256, 1) void mat_decode_kernel(DecParams p) {
   float* QKV0S = WH2 + pad4((size_t)AD * 65);                // [n_tok][3][64] block-0 token table (p.qkv0)
   float* HW4 = QKV0S + (size_t)p.n_tok * 192;                // wide head: [16][AD] float4 of the folded W_h2
   float* HGC = HW4 + (size_t)AD * 64;                        //   then G[AD], C[AD]
-#ifndef MDL_DECODE_SGPR_CARVE
   // the carve's region bases as VGPRs (LDS addresses are VGPR operands anyway): as ~20 uniform SGPR values live
   // across the agent loop they were the bulk of the kernel's SGPR spills (v_writelane / v_readlane + hazard nops)
   KV = lds_v(KV); S = lds_v(S); Q = lds_v(Q); XR = lds_v(XR); XA = lds_v(XA); QT = lds_v(QT); Q2T = lds_v(Q2T);
   LNP = lds_v(LNP); TOK = lds_v(TOK); PEND = lds_v(PEND); EROW = lds_v(EROW); REP = lds_v(REP); AVA = lds_v(AVA);
   RU = lds_v(RU); RN = lds_v(RN); EMB = lds_v(EMB); WH2 = lds_v(WH2); QKV0S = lds_v(QKV0S); HW4 = lds_v(HW4);
   HGC = lds_v(HGC);
-#endif
   constexpr bool stage = STG;
   // wide fused head (one-row discrete passes, 4 < AD <= 64: SMAC's 36 actions): lane a of every wave computes logit a
   // from the folded LayerNorm (p.hfold) and the wave samples with ballots / a prefix scan — replaces the generic head
@@ -511,9 +494,9 @@ __global__ __launch_bounds__(256, 1) void mat_decode_kernel(DecParams p) {
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) bcol[gi] = p.bias[gi * 64 + 16 * wave + c16];
   // folded head (one-row discrete passes, <= 4 actions): this lane's column 16 wave + c16 of W_h2 diag(gamma_h)
-  float hw[SMALL_AD_], hG[SMALL_AD_], hC[SMALL_AD_];
+  float hw[SMALL_AD], hG[SMALL_AD], hC[SMALL_AD];
 #pragma unroll
-  for (int a = 0; a < SMALL_AD_; ++a) {
+  for (int a = 0; a < SMALL_AD; ++a) {
     const bool in = p.hfold && a < AD;
     hw[a] = in ? p.hfold[a * 64 + 16 * wave + c16] : 0.f;
     hG[a] = in ? p.hfold[AD * 64 + a] : 0.f;
@@ -817,7 +800,7 @@ __global__ __launch_bounds__(256, 1) void mat_decode_kernel(DecParams p) {
           const int i = plo;
           const size_t oi = (size_t)env0 * L + i, li = (size_t)i;
           const float lg = rstd * (pa - mean * HGC[ac]) + HGC[AD + ac];
-          const float l = aok ? ((p.ava && AVA[li * AD + ac] == 0.f) ? -1e10f : lg) : -INFINITY;
+          const float l = aok ? ((p.ava && AVA[li * AD + ac] == 0.f) ? MASK_LOGIT : lg) : -INFINITY;
           const float mx = wave_max(l);
           int act = __ffsll((unsigned long long)__ballot(l == mx)) - 1;   // first maximum (argmax)
           const float e = aok ? __expf(l - mx) : 0.f;

@@ -25,7 +25,7 @@
 // logit product (DecParams.hfold), sampling noise comes from in-kernel Philox (same streams as mat_decode.hip).
 #define MDL_LN_ONEPASS 1   // the one-pass LayerNorm forward of mat_train_ct.h, as the decoder's training units
 #include "mat_train_ct.h"
-#include "decode_params.h"
+#include "decode_sample.h"
 
 namespace {
 
@@ -233,16 +233,8 @@ __device__ __forceinline__ CT wv_attn(const bf16_t* Kc, const bf16_t* Vc, const 
   const bf16x8 qb0 = h1 ? z8 : rb(qr, 0), qb1 = h1 ? rb(qr, 1) : z8;
   float m, l;
   f32x4 o[4];
-#ifdef MDL_WV_NOPEEL
-  m = -INFINITY;
-  l = 0.f;
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) o[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb <= i; kb += 32) wv_attn_chunk<false>(Kc, Vc, qb0, qb1, kb, i, lane, m, l, o);
-#else
   wv_attn_chunk<true>(Kc, Vc, qb0, qb1, 0, i, lane, m, l, o);
   for (int kb = 32; kb <= i; kb += 32) wv_attn_chunk<false>(Kc, Vc, qb0, qb1, kb, i, lane, m, l, o);
-#endif
   const float il = 1.f / cross_row_sum(l);
   CT O;
   // columns c < 8 hold head 0 (dims 0..31 = mt 0, 1), c >= 8 head 1 (mt 2, 3): each takes the other half from c ^ 8
@@ -262,11 +254,9 @@ struct WvCtx {
 
 // one decoder block for the live row i (ma_transformer.py:95-98): x <- LN1(x + attn1(x)); x <- LN2(rep_i + attn2(q =
 // rep_i, k = v = x)); x <- LN3(x + mlp(x)).  Block 0's q / K / V of x come from the token table (x = ET[tok]).
-// STQ (the speculative kernel's PAIR main wave): block B's q / K / V rows of x were computed ahead by the speculative
-// wave and staged at stq ([q, k, v][64] bf16): the row's K / V are copied into the caches, the three products skipped
-template <int B, int NB, int NLDS, int NREG, bool STQ = false>
+template <int B, int NB, int NLDS, int NREG>
 __device__ __forceinline__ void wv_block(CT& x, const WvCtx& k, const RegW<NREG>& rw, int i, int tok, const CT& repi,
-                                         const CTr* q2in = nullptr, const bf16_t* stq = nullptr) {
+                                         const CTr* q2in = nullptr) {
   const int lane = k.lane, g = lane >> 4, L = k.L;
   CT xh;
   AFr w;
@@ -283,13 +273,6 @@ __device__ __forceinline__ void wv_block(CT& x, const WvCtx& k, const RegW<NREG>
       }
     }
     x = ld_vec(k.ET + tok * 64, lane);
-  } else if constexpr (STQ) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) qr.q[mt] = *(const uint2*)(stq + 16 * mt + 4 * g);
-    if (lane < 16) {   // lane (kind, 16-byte chunk): staged K / V row -> swizzled cache row i
-      const int kind = lane >> 3, ch = lane & 7;
-      *(uint4*)(wv_cache(k.KV, B, kind, L) + tmo(i, 8 * ch)) = *(const uint4*)(stq + 64 * (kind + 1) + 8 * ch);
-    }
   } else {
     const CTr xp = ct_pack(x);
     CT q = ld_vec(k.BI + 64 * (10 * B + 0), lane), kk = ld_vec(k.BI + 64 * (10 * B + 1), lane);
@@ -350,22 +333,6 @@ __device__ __forceinline__ void wv_block(CT& x, const WvCtx& k, const RegW<NREG>
     ln_fwd_ct(t, xh, x, ld_vec(k.LP + (3 * B + 2) * 128, lane), ld_vec(k.LP + (3 * B + 2) * 128 + 64, lane));
     WDBG(6 * B + 5, x);
   }
-}
-
-// inclusive prefix sum over the 64 lanes (DPP row shifts, then the lower rows' totals)
-__device__ __forceinline__ float wv_incl_scan(float x, int lane) {
-  x += dppf<0x111>(x);
-  x += dppf<0x112>(x);
-  x += dppf<0x114>(x);
-  x += dppf<0x118>(x);
-  const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 15));
-  const float t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 31));
-  const float t2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 47));
-  const int r = lane >> 4;
-  return x + ((r >= 1 ? t0 : 0.f) + (r >= 2 ? t1 : 0.f) + (r >= 3 ? t2 : 0.f));
-}
-__device__ __forceinline__ float rdlane(float x, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
 }
 
 // Phase profile (-DMDL_SPEC_PROF, scripts/spec_prof.py): s_memtime cycles per phase of the main wave and of the first
@@ -483,6 +450,7 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
 #endif
   if (hp) SPH(11);
   const size_t oi = (size_t)env * L + i;
+  const auto u_row = [&] { return rdlane(i < 64 ? nz.U[0] : i < 128 ? nz.U[1] : nz.U[2], i & 63); };   // row i's draw
   float a_out, lp_out;
   if constexpr (!WIDE) {   // A <= 4: the logits are registers r < A of lanes g = 0
     float l[4];
@@ -493,7 +461,7 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
       int amax = 0;
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        l[a] = a < A ? (rdlane(avl, a) == 0.f ? -1e10f : l[a]) : -INFINITY;
+        l[a] = a < A ? (rdlane(avl, a) == 0.f ? MASK_LOGIT : l[a]) : -INFINITY;
         if (l[a] > mx) { mx = l[a]; amax = a; }
       }
       float e[4], se = 0.f;
@@ -502,7 +470,7 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
       const float lse = mx + __logf(se);
       int act = amax;
       if (!det) {
-        const float uu = rdlane(i < 64 ? nz.U[0] : i < 128 ? nz.U[1] : nz.U[2], i & 63);
+        const float uu = u_row();
         const float inv = 1.f / se;
         float cdf = 0.f;
         int cnt = 0, last = -1;
@@ -512,7 +480,6 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
           cnt += (a < A) & (cdf < uu);
           last = (a < A && l[a] > MASKED_BELOW) ? a : last;
         }
-        // a draw above the rounded CDF's last edge takes the last AVAILABLE action (the CDF is flat over masked ones)
         act = min(cnt, last < 0 ? A - 1 : last);
       }
       float la = l[0];
@@ -523,10 +490,7 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
       tok = 1 + act;
     } else {
       const float mu = A == 1 ? l[0] : A == 2 ? l[1] : A == 3 ? l[2] : l[3];
-      const float sd = p.stdv[A - 1];
-      a_out = det ? mu : mu + sd * nz.zlast;
-      const float z = (a_out - mu) / sd;
-      lp_out = -0.5f * z * z - __logf(sd) - 0.91893853320467274f;
+      lp_out = normal_sample_lp(mu, p.stdv[A - 1], nz.zlast, det, a_out);
     }
   } else {   // 4 < A <= 64: logits through LDS, lane a = action a
     if (c == 0) {
@@ -538,25 +502,14 @@ __device__ __forceinline__ int wv_head_sample(const CT& x, const WvHeadW<MA>& hw
     const float raw = SC[lane];
     asm volatile("" ::: "memory");   // the next row's writes stay behind these reads
     if (i < n_disc) {
-      const float l = aok ? (avl == 0.f ? -1e10f : raw) : -INFINITY;
-      const float mx = wave_max(l);
-      int act = __ffsll((unsigned long long)__ballot(l == mx)) - 1;   // first maximum (argmax)
-      const float lse = mx + __logf(wave_sum(aok ? __expf(l - mx) : 0.f));
-      if (!det) {   // inverse CDF: the number of actions whose running probability is below u
-        const float cdf = wv_incl_scan(aok ? __expf(l - lse) : 0.f, lane);
-        const float uu = rdlane(i < 64 ? nz.U[0] : i < 128 ? nz.U[1] : nz.U[2], i & 63);
-        const unsigned long long avm = (unsigned long long)__ballot(aok && l > MASKED_BELOW);   // available actions
-        act = min((int)__popcll((unsigned long long)__ballot(aok && cdf < uu)), avm ? 63 - __clzll(avm) : A - 1);
-      }
-      act = __builtin_amdgcn_readfirstlane(act);
+      const float l = aok ? mask_logit(avl == 0.f, raw) : -INFINITY;
+      float lse;
+      const int act = cat_wave(l, aok, A, u_row, det, lane, lse);
       a_out = (float)act;
       lp_out = rdlane(l, act) - lse;
       tok = 1 + act;
     } else {
-      const float mu = rdlane(raw, A - 1), sd = p.stdv[A - 1];
-      a_out = det ? mu : mu + sd * nz.zlast;
-      const float z = (a_out - mu) / sd;
-      lp_out = -0.5f * z * z - __logf(sd) - 0.91893853320467274f;
+      lp_out = normal_sample_lp(rdlane(raw, A - 1), p.stdv[A - 1], nz.zlast, det, a_out);
     }
   }
   if (hp) SPH(12);
@@ -672,20 +625,6 @@ __global__ __launch_bounds__(64, 1) void mat_decode_wave_kernel(DecParams p) {
 struct SpLds { int w, kv, q2, qt, bi, lp, sc, slot, stg, tok, rowtok, total; };
 // Q2F (L = 129): no cross-attention query table either — the main wave computes block 1's query of its row from
 // W_q2 (one more LDS matrix), the speculative waves block 0's from a register copy of W_q2
-// PAIR (act_dim <= 2): MDL_SPEC_PAIR=0 builds keep the 16-candidate layout (A/B).  MDL_SPEC_STQ=1 (A/B, off: 256 x 33
-// 147.2 -> 151.5 us, 256 x 101 534 -> 528, 256 x 129 720 -> 697 us — the speculative wave became the critical path at
-// the headline shape): PAIR also stages block 1's q / k / v rows of every candidate and the main wave skips them
-#ifndef MDL_SPEC_PAIR
-#define MDL_SPEC_PAIR 1
-#endif
-#ifndef MDL_PAIR_ROR_OLD
-#define MDL_PAIR_ROR_OLD 0
-#endif
-#ifndef MDL_SPEC_STQ
-#define MDL_SPEC_STQ 0
-#endif
-// (when block 1's q / k / v weights are LDS-resident: at most 6 main-wave register matrices)
-__host__ __device__ inline bool sp_stq(int A, int nreg) { return MDL_SPEC_STQ && MDL_SPEC_PAIR && A <= 2 && nreg <= 6; }
 __host__ __device__ inline SpLds sp_lds(int NB, int L, int n_tok, int nlds_main, int A, bool ind, bool q2f = false) {
   SpLds o;
   int off = 0;
@@ -698,8 +637,7 @@ __host__ __device__ inline SpLds sp_lds(int NB, int L, int n_tok, int nlds_main,
   o.lp = take((3 * NB + 1) * 512);
   o.sc = take(64 * 4);
   o.slot = take(2 * A * 256);                // [parity][candidate][64] f32 block-0 outputs
-  o.stg = take(2 * A * (sp_stq(A, wv_nm(NB) - 6 - nlds_main) ? 640 : 256));   // [parity][candidate][rows][64] bf16: block 0's cross K / V
-                                                    // (+ block 1's q, k, v: PAIR)
+  o.stg = take(2 * A * 256);                 // [parity][candidate][K, V][64] bf16: block 0's cross-attention rows
   o.tok = take(16);                          // [parity] token of the next row
   o.rowtok = take(ind ? ((L + 31) & ~31) * 4 : 0);   // IND: input token of every committed row (0 beyond)
   o.total = off;
@@ -883,12 +821,8 @@ __device__ __forceinline__ CT sp_attn_pair(const KVS& kvs, const CTr& q, const C
   // row_ror:N moves a value N lanes UP the row (lane c reads lane c - N mod 16, tests/native/dpp_ror_probe.hip), so
   // "from c + 4" is row_ror:12 and "from c - 4" row_ror:4.  (Rounds 5: the two were swapped — each candidate took the
   // OTHER candidate's second head, invisible with near-identical candidates (random-init weights) but 0.1 nats of
-  // log-prob error per row with a trained policy; MDL_PAIR_ROR_OLD=1 rebuilds that variant for the A/B check.)
-#if MDL_PAIR_ROR_OLD
-  constexpr int ROR_UP = 0x124, ROR_DN = 0x12C;
-#else
+  // log-prob error per row with a trained policy.)
   constexpr int ROR_UP = 0x12C, ROR_DN = 0x124;
-#endif
   O.v[2] = dpp_banks4<ROR_UP, 0x5>(O.v[2]);
   O.v[3] = dpp_banks4<ROR_UP, 0x5>(O.v[3]);
   O.v[0] = dpp_banks4<ROR_DN, 0xA>(O.v[0]);
@@ -1013,8 +947,7 @@ __global__ __launch_bounds__(64 * (1 + NS), 1) void mat_decode_spec_kernel(DecPa
   float* SLOT = (float*)(smem + lo.slot);
   bf16_t* STG = (bf16_t*)(smem + lo.stg);
   int* TOK = (int*)(smem + lo.tok);
-  constexpr bool STQ = MDL_SPEC_STQ && PAIR && NREG <= 6;   // = sp_stq
-  constexpr int SR = STQ ? 320 : 128;     // staged bf16 elements per candidate
+  constexpr int SR = 128;   // staged bf16 elements per candidate
   const float* rep = p.rep + (size_t)env * L * 64;
 
   // ---------------------------------------------------------------- setup (all waves)
@@ -1077,14 +1010,13 @@ __global__ __launch_bounds__(64 * (1 + NS), 1) void mat_decode_spec_kernel(DecPa
       const float avl = (ava && lane < A) ? ava[(size_t)i * A + lane] : 1.f;
       const int cidx = (i & 1) * A + (i == 0 ? 0 : tok - 1);
       CT x = ld_vec(SLOT + (size_t)cidx * 64, lane);
-      const bf16_t* stq = STG + (size_t)cidx * SR + 128;   // PAIR: the staged q / k / v of block 1
       if constexpr (Q2F) {
         AFr wq;
         wv_getw<0, 1, 0>(wq, RegW<0>{}, Wl + (size_t)(NLDS - 6) * 4096, lane);
         const CTr q2 = sp_q2(wq, BI + 64 * (10 * 1 + 4), repi, lane);
-        wv_block<1, NB, NLDS, NREG, STQ>(x, k, rw, i, tok, repi, &q2, stq);
+        wv_block<1, NB, NLDS, NREG>(x, k, rw, i, tok, repi, &q2);
       } else if constexpr (NB > 1) {
-        wv_block<1, NB, NLDS, NREG, STQ>(x, k, rw, i, tok, repi, nullptr, stq);
+        wv_block<1, NB, NLDS, NREG>(x, k, rw, i, tok, repi);
       }
       SPP(1);   // 1: slot read + block 1
 #ifdef MDL_SPEC_PROF
@@ -1126,23 +1058,6 @@ __global__ __launch_bounds__(64 * (1 + NS), 1) void mat_decode_spec_kernel(DecPa
     const int cand = PAIR ? c >> 3 : 16 * (wave - 1) + c;
     const bool own = cand < A && (!PAIR || (c & 7) == 0);
     auto stage = [&](int par, const CT& x, const CTr& kp, const CTr& vp) {
-      CTr pr[3];   // PAIR: block 1's q / k / v of the candidate's block-0 output (weights: the main wave's LDS slots)
-      if constexpr (STQ && NB > 1) {
-        const CTr xp = ct_pack(x);
-        AFr w;
-        wv_getw<wv_slot(1, 0), NLDS, 0>(w, RegW<0>{}, k.W, lane);
-        CT t0 = ld_vec(BI + 64 * 10, lane);
-        mm(t0, w, xp);
-        wv_getw<wv_slot(1, 1), NLDS, 0>(w, RegW<0>{}, k.W, lane);
-        CT t1 = ld_vec(BI + 64 * 11, lane);
-        mm(t1, w, xp);
-        wv_getw<wv_slot(1, 2), NLDS, 0>(w, RegW<0>{}, k.W, lane);
-        CT t2 = ld_vec(BI + 64 * 12, lane);
-        mm(t2, w, xp);
-        pr[0] = ct_pack(t0);
-        pr[1] = ct_pack(t1);
-        pr[2] = ct_pack(t2);
-      }
       if (own) {
         float* sl = SLOT + (size_t)(par * A + cand) * 64;
         bf16_t* st = STG + (size_t)(par * A + cand) * SR;
@@ -1151,10 +1066,6 @@ __global__ __launch_bounds__(64 * (1 + NS), 1) void mat_decode_spec_kernel(DecPa
           *(f32x4*)(sl + 16 * mt + 4 * g) = x.v[mt];
           *(uint2*)(st + 16 * mt + 4 * g) = kp.q[mt];
           *(uint2*)(st + 64 + 16 * mt + 4 * g) = vp.q[mt];
-          if constexpr (STQ && NB > 1) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *(uint2*)(st + 128 + 64 * j + 16 * mt + 4 * g) = pr[j].q[mt];
-          }
         }
       }
     };
@@ -1213,7 +1124,7 @@ int sp_launch_wide(const DecParams* p, size_t lds, hipStream_t st) {   // 3..4 n
 }
 template <int NB, int NS, int NREG, int MA, bool IND = false, bool Q2F = false>
 int sp_launch(const DecParams* p, size_t lds, hipStream_t st) {
-  constexpr bool PAIR = MDL_SPEC_PAIR && NS == 1 && MA == 1;
+  constexpr bool PAIR = NS == 1 && MA == 1;
   if (PAIR && p->act_dim > 2) return sp_launch_wide<NB, NS, NREG, MA, IND, Q2F>(p, lds, st);
   hipError_t e = hipFuncSetAttribute((const void*)mat_decode_spec_kernel<NB, NS, NREG, MA, IND, Q2F, PAIR>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

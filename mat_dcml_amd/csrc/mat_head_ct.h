@@ -124,8 +124,6 @@ __device__ __forceinline__ HeadStat head_stats(const PT& p, const f32x4* L, unsi
   return st;
 }
 
-constexpr float HALF_LOG_2PI = 0.91893853320467274f;
-
 // Normal-head std = sigmoid(log_std) * 0.5 (transformer_act.py:6, ma_transformer.py action std), from the parameter
 // itself (round 1 read a per-minibatch torch copy: three launches per minibatch)
 template <typename PT>
