@@ -6,8 +6,11 @@
 //   step  — DCML_BID_FIRST_MA_ENV_SingleProcess.py:57-144 + Worker.process (DCML_Worker_TIMESLOT_MultiProcess.py:46-112)
 //   reset — DCML_BID_FIRST_MA_ENV_SingleProcess.py:157-274 (+ DCML_Master.reset, Worker.bid)
 // Draw-for-draw identical to the torch path (mat_dcml_amd/envs/dcml/vec_env.py): same Philox counters, same
-// float32 rounding for the bid profile (explicit __fmul_rn/__fadd_rn: no FMA contraction), worker maths in
-// double.  The K-th order statistic is a rank count over the selected workers' delays staged in LDS.
+// float32 rounding for the bid profile, worker maths in double.  Bid profile rule, shared with the torch path: the
+// noise 0.8 + 0.4 u is ONE fused multiply-add (fmaf: one rounding; the reference draws it in float64 with no
+// intermediate rounding, Worker :39), its product with the profile is rounded once, and only the clamp follows, so
+// nothing is left that the build's -ffp-contract=fast could contract.
+// The K-th order statistic is a rank count over the selected workers' delays staged in LDS.
 #include "common.h"
 
 using namespace mdl;
@@ -146,7 +149,7 @@ __device__ void env_reset(const EnvCfg& c, const EnvState& s, int e) {
     for (int i = 0; i < wid; ++i) before += __popcll(s_ballot[i]);
     before += __popcll(s_ballot[wid] & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
   }
-  // bid profile: clip(profile * U(0.8,1.2), 0, 1) in float32, no contraction
+  // bid profile: clip(profile * U(0.8,1.2), 0, 1) in float32
   float l0 = 0.f, l1 = 0.f, l2 = 0.f;
   if (w < W) {
     float* lwp = s.lw + ((size_t)e * W + w) * P;
@@ -154,7 +157,7 @@ __device__ void env_reset(const EnvCfg& c, const EnvState& s, int e) {
       u4 un = philox4x32_10(ctr, g, (uint32_t)w + ((uint32_t)k << 16), P_NOISE, c.k0, c.k1);
       uint32_t uu[4] = {un.x, un.y, un.z, un.w};
       for (int j = 0; j < 4 && 4 * k + j < P; ++j) {
-        const float nf = __fadd_rn(__fmul_rn(u01_open_f(uu[j]), 0.4f), 0.8f);
+        const float nf = fmaf(u01_open_f(uu[j]), 0.4f, 0.8f);   // one rounding: see the header
         float v = __fmul_rn(s.profiles[w * P + 4 * k + j], nf);
         v = fminf(fmaxf(v, 0.f), 1.f);
         lwp[4 * k + j] = v;

@@ -29,6 +29,11 @@ from ...utils import philox as px
 from .config import DCMLConfig
 from .data import load_preset, load_profiles
 
+# limits of the HIP env kernel (csrc/dcml_env.hip MAXW / MAXP: one lane per worker, LDS staging sized by them)
+MAX_KERNEL_WORKERS = 256
+MAX_KERNEL_PERIOD = 64
+_F32_04, _F32_08 = float(np.float32(0.4)), float(np.float32(0.8))   # the kernel's 0.4f / 0.8f as exact doubles
+
 
 class DeviceDCMLEnv:
     """Batched DCML env.  All state lives on ``device``; outputs are device tensors."""
@@ -41,6 +46,12 @@ class DeviceDCMLEnv:
         self.W = self.cfg.n_workers
         self.A = self.cfg.n_agents
         self.P = self.cfg.period
+        # the kernel refuses more (mdl_dcml_env_reset / _step return -1): "auto" takes the torch path instead,
+        # an explicit "hip" is an error here and not at the first reset()
+        fits = self.W <= MAX_KERNEL_WORKERS and self.P <= MAX_KERNEL_PERIOD
+        if backend == "hip" and not fits:
+            raise RuntimeError(f"DCML env kernel handles at most {MAX_KERNEL_WORKERS} workers and a period of "
+                               f"{MAX_KERNEL_PERIOD} (got {self.W} workers, period {self.P})")
         self.device = torch.device(device)
         self.seed = int(seed)
         self.k0, self.k1 = px.seed_key(seed)
@@ -78,7 +89,7 @@ class DeviceDCMLEnv:
         self._kern = None
         if backend in ("auto", "hip") and self.device.type == "cuda":
             from ...ops import kernels
-            if kernels.available() or backend == "hip":
+            if fits and (kernels.available() or backend == "hip"):
                 self._kern = kernels.lib()
 
     # ------------------------------------------------------------------ spaces (reference API shape)
@@ -123,6 +134,11 @@ class DeviceDCMLEnv:
     def reset(self):
         self.counter.zero_()
         self.preset_idx.copy_(self.preset_start)
+        # constant links: reset() re-establishes them like every other state tensor (on an env-range view these, like
+        # the counters above, are the view's rows of the parent's storage: a view resets its own envs only)
+        if not self.cfg.shannon:
+            self.rate.fill_(self.cfg.data_rate)
+            self.up_rate.fill_(self.cfg.data_rate)
         self._reset(torch.ones(self.E, dtype=torch.bool, device=self.device))
         return self.obs, self.share_view(), self.ava
 
@@ -220,7 +236,9 @@ class DeviceDCMLEnv:
             noise.extend(un)
         noise = torch.stack(noise[:P], -1)  # (E, W, P) uint32
         nf = ((noise >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
-        nf = nf * 0.4 + 0.8
+        # 0.8 + 0.4 u with ONE rounding, as the kernel's fmaf: the fp32 factors' product and its sum with fl(0.8) are
+        # exact in fp64 (an integer below 2^51 times 2^-50), so the cast is the only rounding
+        nf = (nf.double() * _F32_04 + _F32_08).float()
         lw = torch.clamp(self.profiles.view(1, W, P) * nf, 0.0, 1.0)
         m = mask
         self.task_ctr = torch.where(m, ctr, self.task_ctr)

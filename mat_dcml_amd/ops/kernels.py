@@ -528,9 +528,10 @@ class SmacOut(ctypes.Structure):
 sig("mdl_smac_env", ctypes.POINTER(SmacCfg), ctypes.POINTER(SmacState), ctypes.POINTER(SmacState), ctypes.POINTER(SmacOut), vp)
 
 
-def smac_env(env, actions):
+def smac_env(env, actions, out=None):
     """One launch of csrc/smac_env.hip: the step (``actions`` (E, A) policy rows) or, with ``actions=None``, the
-    reset of every env; returns (obs, state, ava, reward (E,), dones (E, A) bool, info)."""
+    reset of every env; returns (obs, state, ava, reward (E,), dones (E, A) bool, info).  ``out`` = (obs, state, ava)
+    float32 contiguous tensors to write into instead of fresh ones (the kernel overwrites every element)."""
     E, A, N, sp = env.E, env.A, env.N, env.spec
     dev = env.device
     for name in ("apos", "ahp", "epos", "ehp"):
@@ -552,9 +553,14 @@ def smac_env(env, actions):
     s = SmacState(*[getattr(env, n).data_ptr() for n in names])
     so = SmacState(env.gid.data_ptr(), *[spare[n].data_ptr() for n in names[1:]])
     f32 = dict(device=dev, dtype=torch.float32)
-    obs = torch.empty(E, A, sp.obs_dim, **f32)
-    state = torch.empty(E, A, sp.state_dim, **f32)
-    ava = torch.empty(E, A, env.n_actions, **f32)
+    if out is not None:
+        obs, state, ava = out
+        for t, n in ((obs, sp.obs_dim), (state, sp.state_dim), (ava, env.n_actions)):
+            assert t.shape == (E, A, n) and t.dtype == torch.float32 and t.is_contiguous() and t.device.type == dev.type, t.shape
+    else:
+        obs = torch.empty(E, A, sp.obs_dim, **f32)
+        state = torch.empty(E, A, sp.state_dim, **f32)
+        ava = torch.empty(E, A, env.n_actions, **f32)
     reward = torch.empty(E, **f32)
     dones = torch.empty(E, A, dtype=torch.bool, device=dev)
     flags = torch.empty(3, E, dtype=torch.bool, device=dev)
